@@ -5,7 +5,7 @@ N = 1 : configs[1] -- 3D 7-pt Poisson 256^3, single-block GMRES(30), pc none,
         one step = one KSPSolve from x0 = 0 with the canonical options
         (running_bulk_test_g5k:64-70: rtol 1e-4, unpreconditioned norm) and a
         fixed max_it = 300 (10 restart cycles).
-        The same JSON line also carries, each measured in this run:
+        With --full the same JSON line also carries, each measured in this run:
           smsm_per_gpu  the N > 1 workload below on one GPU (one 512x512x256
                         block), so that N -> 8 compares SMSM with SMSM;
           spmv_512_csr  the north star's "CSR SpMV on the 512^3 7-point
@@ -33,6 +33,15 @@ value = sum over blocks of (rows x inner GMRES iterations) / max-over-ranks time
 
 Launch: python bench.py [--gpus N --steps K --warmup W]   (N > 1 under
 torch.distributed.run, one rank per GPU, RCCL = backend "nccl").
+
+A plain run sets up, warms up, times the K steps (ms_per_step = their wall time
+/ K; the per-kernel HIP events ride inside them), writes the last step's result
+with --dump-outputs DIR, and prints the line.  --full adds, after the timed
+steps: the check of the timed result against the committed oracle records
+(verified, verification), the CSR-storage rerun, the N = 1 side measurements
+listed above with seq_mode, smsm_seq_mode, assembled_csr_operator and
+non_stencil_aij, the CPU baseline, and at N > 1 the multi-rank check; a --full
+run exits non-zero when one of its checks fails.
 """
 from __future__ import annotations
 
@@ -92,6 +101,16 @@ def parse():
     p.add_argument("--max-it", type=int, default=300)
     p.add_argument("--restart", type=int, default=30)
     p.add_argument("--rtol", type=float, default=1e-4)
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps, also run everything beside the headline figure: the check of the "
+                        "timed result against the committed oracle records, the CSR-storage rerun, the side "
+                        "measurements of an N = 1 run (each has its own --no-... switch), the CPU baseline, and at "
+                        "N > 1 the multi-rank check.  Without it a run sets up, warms up, times --steps steps and "
+                        "prints its line")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64): "
+                        "the solution x (a fixed, seeded sample of it when it exceeds DUMP_MAX_BYTES) and the step's "
+                        "residual history; at N > 1 every rank writes its block as <name>_rank<r>.npy")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-sample-its", type=int, default=30)
     p.add_argument("--no-timing", action="store_true", help="disable per-kernel HIP-event timing")
@@ -262,6 +281,27 @@ def load_traffic():
         return json.load(open(p))
     except Exception:
         return None
+
+
+DUMP_MAX_BYTES = 32 << 20      # per array; a run writes two or three arrays, the small ones a few KB
+DUMP_SEED = 20251121
+
+
+def dump_outputs(dirname, arrays, suffix=""):
+    """--dump-outputs: every array of the last timed step as dirname/<name><suffix>.npy in float64.  An array above
+    DUMP_MAX_BYTES is written as a fixed sample: its entries at DUMP_MAX_BYTES / 8 indices drawn once from
+    default_rng(DUMP_SEED) and sorted, the same indices for the same length in every run and every build."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    written = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, np.float64).ravel()
+        if a.nbytes > DUMP_MAX_BYTES:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, a.size, DUMP_MAX_BYTES // 8))
+            a = a[idx]
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), a)
+        written[f"{name}{suffix}.npy"] = int(a.size)
+    return written
 
 
 # ------------------------------------------------------------------ workloads
@@ -814,6 +854,9 @@ def main():
         def step():
             ksp.solve(b, x)                     # zero initial guess: x is reset by KSPSolve
             return ksp.get_iteration_number()
+
+        def outputs():
+            return {"x": x.get_array(), "residual_history": ksp.get_residual_history()}
         workload = f"3D 7-pt Poisson {n}^3, single-block GMRES({args.restart}) on 1 MI355X (configs[1])"
         if args.operator == "matfree":
             workload += ", operator applied matrix-free (same arithmetic as the CSR; not the reference's MatMult)"
@@ -832,6 +875,9 @@ def main():
             sq = blk.local_residual_sq()
             comm.ordered_sum([blk], [sq])
             return its
+
+        def outputs():
+            return {"x": blk.x.get_array(), "residual_history": blk.ksp.get_residual_history()}
         workload = (f"3D 7-pt Poisson {n}x{n}x{n * world} synchronous multisplitting, {world} z-slab blocks of "
                     f"{n}^3 (one per MI355X), inner GMRES({args.restart}) max_it {args.max_it}, "
                     f"{'library RCCL communicator' if world > 1 else 'single block'}")
@@ -853,6 +899,9 @@ def main():
                          stop_at_limit=True)
             amres.append(r)
             return sum(r.inner_its)
+
+        def outputs():
+            return {"x": blk.x.get_array(), "inner_iterations": amres[-1].inner_its}
         workload = (f"3D 7-pt {'upwind convection-diffusion' if args.peclet else 'Poisson'} {n}x{n}x{nz} AMAM-global, "
                     f"{world} z-slab block(s) of {n}x{n}x{args.amam_planes} (one per MI355X; "
                     f"{'configs[4]' if args.peclet else 'configs[3]'} per-GPU block), s = {args.s} inner GMRES("
@@ -864,6 +913,10 @@ def main():
     else:
         step, workload, kspopts, rows, (blk, mini, lsqr_its) = build_smsm(ctx, args, comm, world, rank)
         n = args.smsm_mesh
+
+        def outputs():
+            return {"x": blk.x.get_array(), "lsqr_residual_norm": step.lsqr_rnorm[-1:],
+                    "inner_iterations": step.inner_its[-args.s:]}
 
     if args.peclet is not None:
         workload = workload.replace("7-pt Poisson", "7-pt upwind convection-diffusion (cell Peclet "
@@ -888,15 +941,19 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     stats = ctx.kernel_stats() if timing else {}
+    dumped = None
+    if args.dump_outputs and args.steps > 0:
+        # what the last timed step left, before anything below runs the solver again
+        dumped = dump_outputs(args.dump_outputs, outputs(), f"_rank{rank}" if world > 1 else "")
 
-    # the result of the last timed step against the committed oracle record (outside the timed region)
+    # --full: the result of the last timed step against the committed oracle record (outside the timed region)
     verified, mismatch, ref_ranks = None, [], None
-    ref = golden_configs1(args, n) if variant == "gmres" and world == 1 else None
+    ref = golden_configs1(args, n) if args.full and variant == "gmres" and world == 1 else None
     if ref is not None:
         verified, mismatch = check_step(ksp, x, ref["dbr"])
 
     csr_same_run = None
-    if (variant == "gmres" and world == 1 and args.operator == "csr" and args.storage == "dv"
+    if (args.full and variant == "gmres" and world == 1 and args.operator == "csr" and args.storage == "dv"
             and not args.no_csr_compare):
         # the same workload with the matrix in CSR storage, same process, same timing setting
         A.set_storage("csr")
@@ -922,7 +979,7 @@ def main():
         dist.all_reduce(t[1:], op=dist.ReduceOp.SUM)
         elapsed_max, updates = float(tmax[0]), float(t[1])
         timed_check = None
-        if variant == "smsm" and world == 2:
+        if args.full and variant == "smsm" and world == 2:
             # N = 2 is configs[2] itself (512^3, two blocks): the run's own outer iterations -- warm-up and timed --
             # against the oracle record of that problem, as far as the record goes (it ends where configs[2]
             # converges); every rank checks its block's inner counts, the verdict is all ranks'
@@ -937,7 +994,7 @@ def main():
                            "reference": "tests/golden/configs2_smsm.json['cubes']['512'] (oracle/oracle.c "
                                         "orc_smsm_solve, DBR order, lean): every outer LSQR residual (hex), LSQR "
                                         "count and inner count of the run's first outer iterations"}
-        if not args.no_verify_ranks:
+        if args.full and not args.no_verify_ranks:
             # collective on every rank, after the timed loop and outside it
             verified, vmis, vsec = verify_ranks(ctx, comm, world, rank)
             ref_ranks = {"reference": "tests/golden/smsm_ranks.json (oracle/oracle.c orc_smsm_solve, DBR order)",
@@ -949,7 +1006,7 @@ def main():
         elapsed_max, updates = elapsed, my_updates
 
     extras = {}
-    if world == 1 and variant == "gmres" and rank == 0:
+    if args.full and world == 1 and variant == "gmres" and rank == 0:
         if not args.no_seq_mode and ref is not None:
             extras["seq_mode"] = seq_mode_step(ctx, ksp, b, x, ref)
         if not args.no_assembled and args.operator == "csr" and args.peclet is None:
@@ -978,7 +1035,9 @@ def main():
                           "matrix_storage": "none (matrix-free)" if args.operator == "matfree" else args.storage,
                           "parallelism": f"{world} z-slab block(s), one per GPU",
                           "transport": transport},
-               "verified": verified}
+               "verified": verified, "full": args.full}
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "entries": dumped}
         if ref_ranks is not None:
             out["verification"] = ref_ranks
         if world > 1 and timed_check is not None:
@@ -1030,7 +1089,7 @@ def main():
             # sampled launches stand for timing_every launches each
             out["hbm_alg_GBps_whole_step"] = alg_bytes * max(1, args.timing_every) / elapsed / 1e9
         out.update(extras)
-        if world == 1 and variant == "gmres" and not args.no_cpu_baseline and args.peclet is None:
+        if args.full and world == 1 and variant == "gmres" and not args.no_cpu_baseline and args.peclet is None:
             out["cpu_baseline"] = cpu_baseline(n, args.restart, args.cpu_sample_its, args.rtol)
         else:
             out["cpu_baseline"] = None

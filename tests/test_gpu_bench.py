@@ -13,8 +13,8 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMALL = ["--variant", "smsm", "--smsm-mesh", "64", "--smsm-planes", "16", "--steps", "1", "--warmup", "0",
-         "--no-timing"]
+SMALL = ["--full", "--variant", "smsm", "--smsm-mesh", "64", "--smsm-planes", "16", "--steps", "1", "--warmup", "0",
+         "--no-timing"]   # --full: the post-timing checks these tests read belong to a full run
 
 
 def _port():
@@ -74,7 +74,7 @@ def test_require_rccl_refuses_host_transport():
 def test_single_gpu_line_is_verified():
     """N = 1: the timed GMRES step (configs[1]) equals the committed DBR oracle record -- iterations, reason, every
     history entry, SHA-256 of x -- and the line says verified: true; the CSR-storage rerun is verified too."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "1", "--warmup", "0",
                         "--no-smsm-n1", "--no-spmv512", "--no-cpu-baseline", "--no-seq-mode", "--no-seq-smsm"],
                        capture_output=True, text=True, timeout=240, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]

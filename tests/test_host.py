@@ -166,7 +166,7 @@ def test_bench_reads_the_measured_streaming_ceiling():
 
 
 def test_bench_smsm_seq_line_reads_its_record():
-    """bench.py's smsm_seq_mode line (in every N = 1 run; --no-seq-smsm skips it) checks the fields of
+    """bench.py's smsm_seq_mode line (in every N = 1 --full run; --no-seq-smsm skips it) checks the fields of
     tests/golden/smsm_seq.json that smsm_solve reports, at the block and options the record names."""
     import importlib
     import json
@@ -184,6 +184,30 @@ def test_bench_smsm_seq_line_reads_its_record():
         assert not bench.parse().no_seq_smsm
     finally:
         sys.argv = old
+
+
+def test_bench_plain_run_options_and_output_dump(tmp_path, monkeypatch):
+    """--full is off by default, and --dump-outputs writes float64 .npy files: a small array whole, one above
+    DUMP_MAX_BYTES as the same seeded sample of its entries in every call."""
+    import importlib
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    bench = importlib.import_module("bench")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "2"])
+    a = bench.parse()
+    assert not a.full and a.dump_outputs is None and (a.steps, a.warmup) == (3, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", str(tmp_path)])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == str(tmp_path)
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 8 * 1000)
+    big = np.arange(5000, dtype=np.float64) * 0.5
+    for d in ("a", "b"):
+        w = bench.dump_outputs(str(tmp_path / d), {"x": big, "residual_history": [3.0, 2.0, 1.0]}, "_rank1")
+        assert w == {"x_rank1.npy": 1000, "residual_history_rank1.npy": 3}
+    xa, xb = np.load(tmp_path / "a" / "x_rank1.npy"), np.load(tmp_path / "b" / "x_rank1.npy")
+    assert xa.dtype == np.float64 and xa.shape == (1000,) and np.array_equal(xa, xb)
+    assert np.all(np.diff(xa) >= 0) and np.all(np.isin(xa, big)) and np.unique(xa).size > 800
+    assert np.array_equal(np.load(tmp_path / "a" / "residual_history_rank1.npy"), [3.0, 2.0, 1.0])
 
 
 def _isolve(args, **env):

@@ -13,6 +13,6 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 timeout -k 10 600 python -u -m pytest tests/test_gpu_bench.py -x -v --timeout 300 --timeout-method thread > $OUT/bench_tests.log 2>&1 &&
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -T -d $OUT/smsm_trace -o run -f csv -- python3 bench.py --variant smsm --steps 2 --warmup 1 > $OUT/bench_smsm_trace.json 2> $OUT/smsm_trace.err &&
-timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 2 --warmup 1 --backend gloo --smsm-planes 128 > $OUT/bench_n2_gloo.json 2> $OUT/bench_n2_gloo.err
+timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --full --steps 2 --warmup 1 --backend gloo --smsm-planes 128 > $OUT/bench_n2_gloo.json 2> $OUT/bench_n2_gloo.err
 echo "exit $?" > $OUT/status
 exit 0

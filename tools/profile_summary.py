@@ -44,7 +44,7 @@ def main():
           "AverageNs": sum(float(r["TotalDurationNs"]) for r in mxs) / calls}
     rf = b["roofline"]
     L = [f"# Round {a.tag[1:]} profiles (MI355X, gfx950, ROCm 7.2)", "",
-         f"Command: `bash tools/gpu_round.sh {os.path.basename(run)}` (or tools/gpu_r02.sh, which adds smoke) = pytest -m gpu; `python bench.py`; "
+         f"Command: `bash tools/gpu_round.sh {os.path.basename(run)}` (or tools/gpu_r02.sh, which adds smoke) = pytest -m gpu; `python bench.py --full`; "
          "`rocprofv3 --kernel-trace --stats -T -- python3 bench.py --steps 3 --no-cpu-baseline`;",
          "two PMC passes (`--pmc FETCH_SIZE`, `--pmc WRITE_SIZE`) of `bench.py --steps 1 --warmup 0 --no-timing`, "
          "reduced by `tools/pmc_traffic.py` (read = 2 x FETCH_SIZE on gfx950, write = WRITE_SIZE). "
