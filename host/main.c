@@ -45,7 +45,8 @@ static int usage(void) {
   fprintf(stderr, "usage: msplit_driver <synchronous-multisplitting | "
                   "synchronous-multisplitting-synchronous-minimization-global | asynchronous-multisplitting | "
                   "asynchronous-multisplitting-asynchronous-minimization-global> "
-                  "-m M -n N [-s S] [-rtol R] [-dim 3 -p P] [-peclet px,py,pz] [-nb B] [-msplit_reduction dbr|seq] [-msplit_minimization lsqr|rtr] [-json] ...\n");
+                  "-m M -n N [-s S] [-rtol R] [-dim 3 -p P] [-peclet px,py,pz] [-nb B] [-msplit_reduction dbr|seq] [-msplit_minimization lsqr|rtr] "
+                  "[-innerK_msplit_basis_precision double|single] [-json] ...\n");
   return 2;
 }
 

@@ -285,6 +285,22 @@ int msp_ksp_get_residual_norm(const msp_ksp *ksp, double *rnorm);     /* KSPGetR
 int msp_ksp_get_converged_reason(const msp_ksp *ksp, int32_t *reason);
 /* Residual history of the last solve (KSPGetResidualHistory): its+1 entries. */
 int msp_ksp_get_residual_history(const msp_ksp *ksp, const double **hist, int32_t *n);
+/* Storage precision of the Krylov basis in HBM (-msplit_basis_precision double|single).
+ * MSP_BASIS_F64 (default): the basis is stored as double.
+ * MSP_BASIS_F32: compressed-basis GMRES.  Each basis vector is rounded to float once, when it is stored
+ * (round to nearest even, gradual underflow, overflow to +-inf), promoted to double as it is read, and its norm
+ * is the norm of the rounded values; the Hessenberg, the rotations, every dot and sum, the operator and x stay
+ * double, and every restart recomputes the true residual in double.  Half the basis bytes per step and per
+ * block.  Entries beyond float range end the solve with MSP_DIVERGED_NANORINF.  DBR reduction only: a solve on a
+ * context in MSP_REDUCE_SEQ returns MSP_ERR_SUP.  Changing the precision frees the work of an earlier set-up.
+ * Any other value: MSP_ERR_ARG_OUTOFRANGE. */
+#define MSP_BASIS_F64 0
+#define MSP_BASIS_F32 1
+int msp_ksp_set_basis_precision(msp_ksp *ksp, int prec);
+int msp_ksp_get_basis_precision(const msp_ksp *ksp, int *prec);
+/* Device bytes the KSP holds once set up and solved with: the basis, W / the current vector, and the recurrence
+ * block (0 before set-up). */
+int msp_ksp_get_work_bytes(const msp_ksp *ksp, int64_t *bytes);
 
 /* ------------------------------------------------------------------ dense */
 /* A block of rows of a MATDENSE / MATMPIDENSE matrix, column-major in HBM with

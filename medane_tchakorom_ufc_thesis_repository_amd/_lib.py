@@ -106,6 +106,9 @@ _SIGS = {
     "msp_ksp_get_residual_norm": [_vp, _dp],
     "msp_ksp_get_converged_reason": [_vp, _i32p],
     "msp_ksp_get_residual_history": [_vp, _P(_dp), _i32p],
+    "msp_ksp_set_basis_precision": [_vp, C.c_int],
+    "msp_ksp_get_basis_precision": [_vp, _P(C.c_int)],
+    "msp_ksp_get_work_bytes": [_vp, _P(C.c_int64)],
     "msp_mat_create_box_stencil_ext": [_vp, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                        _P(_vp)],
     "msp_mat_create_box_matfree": [_vp, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp,

@@ -2,7 +2,7 @@
  * ksp_gmres.c -- KSPGMRES host logic over device-resident Krylov vectors.
  *
  * Restates PETSc 3.22.1's KSPSolve_GMRES / KSPGMRESCycle / classical
- * Gram-Schmidt (REFINE_NEVER) / KSPGMRESUpdateHessenberg / KSPGMRESBuildSoln /
+ * Gram-Schmidt (KSP_GMRES_CGS_REFINE_NEVER: one pass, no refinement) / KSPGMRESUpdateHessenberg / KSPGMRESBuildSoln /
  * KSPConvergedDefault with PCNONE -- the inner solve the reference calls from
  * inner_solver() (src/utils/utils.c:950-970) and gmres_solution.c:70.
  *
@@ -23,13 +23,27 @@
  *   MDot      h(0..it) = W . sc.VV(0..it)            (DBR order)
  *   MAXPY     VV(it+1) = W - sum h_j sc[j] VV(j), and ||VV(it+1)||^2   (one pass)
  *   update    the Hessenberg column, Givens rotation, tests, sc[it+1] (one lane)
- * W is PETSc's VEC_VV(it+1) before the orthogonalisation; keeping it in its own
- * vector makes the MAXPY write a different vector than it reads (an in-place
- * MAXPY measured 5 % slower, same box).
+ * W is PETSc's VEC_VV(it+1) before the orthogonalisation.
  *
- * Data layout: VV(0..min(m, max_it)) are one allocation, (min(m, max_it)+1) x stride doubles, stride =
- * n rounded up to 512 (4 KiB aligned); W is separate.  KSPInitialResidual
- * writes VV(0).
+ * Step kinds (step_kind, asked before every solve).  The four lines above are one arithmetic; which kernels run
+ * them, and whether W ever reaches HBM, depends on the operator and the basis precision:
+ *   opfuse   DV storage in the 8-code ELL layout (MSK_TUNE_GM_OPFUSE): MDot and MAXPY each compute their rows of
+ *            W from the operator's codes; no MatMult kernel, no W vector.
+ *   wfree    box stencils (the default there): the MatMult is fused with MDot and W is not stored; the MAXPY
+ *            recomputes its rows from VV(it).
+ *   stored W every other operator: W is its own n-vector (k->tmp, allocated by the first cycle that needs it),
+ *            written by the MatMult (fused with MDot where the operator allows) and read by the MAXPY, which writes
+ *            a different vector than it reads (an in-place MAXPY measured 5 % slower, same box).
+ *   f32      MSP_BASIS_F32 (msp_ksp_set_basis_precision): the basis is stored as float and the step is always
+ *            MatMult, MDot, MAXPY as three kernels (msplit_cb.hip) over two f64 n-vectors: W and the "current
+ *            vector", the newest basis vector's rounded values as doubles, which is the MatMult's input -- so every
+ *            operator's scaled MatMult serves unchanged.  VV(it+1) = rnd(W - sum ...) is rounded when stored and
+ *            its norm is the rounded values' norm; everything else is the same f64 arithmetic.  Neither opfuse nor
+ *            wfree is taken, and the MDot / MAXPY variant flags of MSPLIT_TUNING do not apply.
+ *
+ * Data layout: VV(0..min(m, max_it)) are one allocation of (min(m, max_it)+1) x stride elements; stride = n rounded
+ * up to 512 doubles, or to 1024 floats (4 KiB either way).  W and the current vector are separate allocations.
+ * KSPInitialResidual writes VV(0) (f32: the current vector, which the cycle's first kernel rounds into VV(0)).
  */
 #include <math.h>
 #include <stdlib.h>
@@ -60,8 +74,11 @@ struct msp_ksp {
   msp_ksp_opts o;
   int setup;
   int64_t n, stride;
-  double *basis;            /* device: (m+1) * stride, stored unnormalised (scales in g.sc) */
+  int basis_prec;           /* MSP_BASIS_F64 / MSP_BASIS_F32: the element type behind basis */
+  double *basis;            /* device: (m+1) * stride, stored unnormalised (scales in g.sc); floats when F32 */
   double *tmp;              /* device: W = A VV(it) before the orthogonalisation */
+  double *cur;              /* device, F32 only: the newest basis vector's rounded values as doubles */
+  size_t basis_bytes, gblock_bytes, vec_bytes; /* sizes of the allocations (vec_bytes: tmp and cur, each) */
   mspi_gmres_dev g;         /* device-resident recurrence state and arrays */
   void *gblock;             /* the single device allocation behind g */
   mspi_gmres_state *hst;    /* pinned host mirror of *g.st */
@@ -117,10 +134,12 @@ static void ksp_free_work(msp_ksp *k) {
   ksp_drop_graphs(k);
   if (k->basis) mspi_free(k->ctx, k->basis);
   if (k->tmp) mspi_free(k->ctx, k->tmp);
+  if (k->cur) mspi_free(k->ctx, k->cur);
   if (k->gblock) mspi_free(k->ctx, k->gblock);
   if (k->hst) mspi_host_free(k->hst);
   free(k->hist);
-  k->basis = k->tmp = NULL;
+  k->basis = k->tmp = k->cur = NULL;
+  k->basis_bytes = k->gblock_bytes = k->vec_bytes = 0;
   k->gblock = NULL;
   k->hst = NULL;
   k->hist = NULL;
@@ -185,6 +204,41 @@ int msp_ksp_get_opts(const msp_ksp *k, msp_ksp_opts *o) {
   return MSP_SUCCESS;
 }
 
+int msp_ksp_set_basis_precision(msp_ksp *k, int prec) {
+  if (!k) {
+    mspi_set_error(MSP_ERR_ARG_NULL, "NULL argument");
+    return MSP_ERR_ARG_NULL;
+  }
+  if (prec != MSP_BASIS_F64 && prec != MSP_BASIS_F32) {
+    mspi_set_error(MSP_ERR_ARG_OUTOFRANGE, "basis precision %d is neither MSP_BASIS_F64 nor MSP_BASIS_F32", prec);
+    return MSP_ERR_ARG_OUTOFRANGE;
+  }
+  if (prec != k->basis_prec && k->setup) { /* another element type: new work vectors, no graph survives */
+    msp_ctx_synchronize(k->ctx);
+    ksp_free_work(k);
+  }
+  k->basis_prec = prec;
+  return MSP_SUCCESS;
+}
+
+int msp_ksp_get_basis_precision(const msp_ksp *k, int *prec) {
+  if (!k || !prec) {
+    mspi_set_error(MSP_ERR_ARG_NULL, "NULL argument");
+    return MSP_ERR_ARG_NULL;
+  }
+  *prec = k->basis_prec;
+  return MSP_SUCCESS;
+}
+
+int msp_ksp_get_work_bytes(const msp_ksp *k, int64_t *bytes) {
+  if (!k || !bytes) {
+    mspi_set_error(MSP_ERR_ARG_NULL, "NULL argument");
+    return MSP_ERR_ARG_NULL;
+  }
+  *bytes = (int64_t)(k->basis_bytes + k->gblock_bytes + (k->tmp ? k->vec_bytes : 0) + (k->cur ? k->vec_bytes : 0));
+  return MSP_SUCCESS;
+}
+
 int msp_ksp_set_up(msp_ksp *k) {
   if (!k || !k->A) {
     mspi_set_error(MSP_ERR_ARG_WRONG, "KSPSetUp before KSPSetOperators");
@@ -198,15 +252,20 @@ int msp_ksp_set_up(msp_ksp *k) {
   const int64_t mv = (k->o.max_it < m ? k->o.max_it : m) + 1;
   int64_t skew = 0; /* an extra skew between basis vectors measured no gain (profiles/r01/skew_ab) */
   const char *env = getenv("MSPLIT_BASIS_SKEW");
-  if (env) skew = (atoll(env) + 511) / 512 * 512;
-  k->stride = (k->n + 511) / 512 * 512 + skew;
+  const int f32 = k->basis_prec == MSP_BASIS_F32;
+  const int64_t align = f32 ? 1024 : 512; /* elements in 4 KiB */
+  if (env) skew = (atoll(env) + align - 1) / align * align;
+  k->stride = (k->n + align - 1) / align * align + skew;
   k->hist_cap = k->o.max_it + 2;
   /* one device block for the recurrence: state, then hh, cc, ss, grs, h, sc, hist */
   const size_t nd = (size_t)((m + 2) * (m + 1) + 5 * (m + 2) + k->hist_cap);
   const size_t st_bytes = (sizeof(mspi_gmres_state) + 63) / 64 * 64;
-  int rc = mspi_malloc(k->ctx, (void **)&k->basis, (size_t)mv * (size_t)k->stride * sizeof(double) + 4096);
+  k->basis_bytes = (size_t)mv * (size_t)k->stride * (f32 ? sizeof(float) : sizeof(double)) + 4096;
+  k->gblock_bytes = st_bytes + nd * sizeof(double);
+  k->vec_bytes = (size_t)((k->n + 511) / 512 * 512) * sizeof(double) + 4096;
+  int rc = mspi_malloc(k->ctx, (void **)&k->basis, k->basis_bytes);
   /* W (k->tmp) is allocated by the first cycle that stores it (ensure_w): the W-free step never does */
-  if (!rc) rc = mspi_malloc(k->ctx, &k->gblock, st_bytes + nd * sizeof(double));
+  if (!rc) rc = mspi_malloc(k->ctx, &k->gblock, k->gblock_bytes);
   if (!rc) rc = mspi_host_malloc((void **)&k->hst, sizeof(mspi_gmres_state));
   k->hist = (double *)calloc((size_t)k->hist_cap, sizeof(double));
   if (!rc && !k->hist) {
@@ -237,11 +296,16 @@ int msp_ksp_set_up(msp_ksp *k) {
 }
 
 static double *VV(const msp_ksp *k, int j) { return k->basis + (int64_t)j * k->stride; }
+static float *VF(const msp_ksp *k, int j) { return (float *)k->basis + (int64_t)j * k->stride; } /* MSP_BASIS_F32 */
 
 /* Which Arnoldi step a cycle runs: the operator computed inside MDot and MAXPY (opfuse), the W-free step on a box
  * stencil (wfree), or W stored between the MatMult and the CGS kernels (neither).  The W-free choice follows the
  * operator and msk_set_gm_wfree, so it is asked again before every solve. */
 static void step_kind(const msp_ksp *k, int *opfuse, int *wfree) {
+  if (k->basis_prec == MSP_BASIS_F32) { /* those kernels read an f64 basis: the f32 step stores W */
+    *opfuse = *wfree = 0;
+    return;
+  }
   *opfuse = mspi_op_fusable(k->A) && k->o.restart + 1 <= MSPI_MAX_GROUP;
   *wfree = !*opfuse && k->o.restart <= MSPI_MAX_GROUP && mspi_gm_wfree(k->A);
 }
@@ -251,8 +315,12 @@ static void step_kind(const msp_ksp *k, int *opfuse, int *wfree) {
 static int ensure_w(msp_ksp *k) {
   int opfuse, wfree;
   step_kind(k, &opfuse, &wfree);
-  if (opfuse || wfree || k->tmp) return MSP_SUCCESS;
-  return mspi_malloc(k->ctx, (void **)&k->tmp, (size_t)k->stride * sizeof(double) + 4096);
+  if (opfuse || wfree) return MSP_SUCCESS;
+  int rc = MSP_SUCCESS;
+  if (!k->tmp) rc = mspi_malloc(k->ctx, (void **)&k->tmp, k->vec_bytes);
+  /* the f32 step's second f64 n-vector: the MatMult's input */
+  if (!rc && k->basis_prec == MSP_BASIS_F32 && !k->cur) rc = mspi_malloc(k->ctx, (void **)&k->cur, k->vec_bytes);
+  return rc;
 }
 
 /* One KSPGMRESCycle from its initial residual in VV(0): VecNormalize (deferred),
@@ -262,10 +330,27 @@ static int enqueue_cycle(msp_ksp *k, double *x, int K) {
   const int *stop = &k->g.st->stop;
   const double *sc = k->g.sc;
   double *sumsq = &k->g.h[0];
-  int rc = mspi_norm2sq(c, VV(k, 0), k->n, sumsq);
+  const int f32 = k->basis_prec == MSP_BASIS_F32;
+  /* f32: the initial residual waits in the current vector; VV(0) = rnd(r), the vector's norm is the rounded one's */
+  int rc = f32 ? mspi_cb_round_store(c, k->cur, k->cur, VF(k, 0), k->n, sumsq, NULL)
+               : mspi_norm2sq(c, VV(k, 0), k->n, sumsq);
   if (!rc) rc = mspi_gm_cycle_start(c, k->g, sumsq);
   int opfuse, wfree;
   step_kind(k, &opfuse, &wfree);
+  for (int it = 0; it < K && !rc && f32; ++it) {
+    /* W = A (sc[it] s_it) from the current vector (s_it as doubles), h = W . sc.VV(0..it) over the float basis,
+     * then s_{it+1} = rnd(W - sum h_j sc[j] VV(j)) to VV(it+1) and back into the current vector, ||s_{it+1}||^2 */
+    rc = mspi_spmv_scaled(k->A, k->cur, sc + it, NULL, k->tmp, stop);
+    if (!rc) rc = mspi_cb_mdot(c, k->tmp, it + 1, VF(k, 0), k->stride, sc, k->n, k->g.h, stop);
+    if (!rc)
+      rc = mspi_cb_maxpy_norm_update(c, k->tmp, k->cur, VF(k, it + 1), it + 1, VF(k, 0), k->stride, sc, k->n, k->g,
+                                     k->o.restart, stop);
+  }
+  if (f32) {
+    if (!rc) rc = mspi_gm_build(c, k->g, (int)k->o.restart);
+    if (!rc) rc = mspi_cb_accum(c, x, &k->g.st->nbuild, VF(k, 0), k->stride, sc, k->n, k->g.grs, K);
+    return rc;
+  }
   for (int it = 0; it < K && !rc && opfuse; ++it) {
     /* W = A (sc[it] VV(it)) never reaches HBM: MDot and MAXPY each compute their rows of it from the operator's
      * one-byte codes and VV(it) (which both stream anyway), bitwise the separate MatMult's W */
@@ -311,6 +396,7 @@ static int run_cycle(msp_ksp *k, double *x, int K) {
   int rc = mspi_reserve_partial(c, k->n); /* before the lookup: it may reallocate (a new epoch) */
   if (rc) return rc;
   const uint64_t aver = mspi_mat_version(k->A), epoch = mspi_ctx_epoch(c);
+  /* the basis precision is not in the key: changing it frees the work, and with it every captured cycle */
   const int tuning = msk_get_tuning(), shape = msk_get_shape_epoch();
   for (int i = 0; i < KSP_NGRAPH; ++i) {
     const ksp_graph *g = &k->graphs[i];
@@ -362,6 +448,11 @@ int msp_ksp_solve(msp_ksp *k, const msp_vec *b, msp_vec *x) {
     mspi_set_error(MSP_ERR_ARG_WRONG, "b and x must be different vectors");
     return MSP_ERR_ARG_WRONG;
   }
+  if (k->basis_prec == MSP_BASIS_F32 && mspi_reduce_seq(k->ctx)) {
+    mspi_set_error(MSP_ERR_SUP, "MSP_BASIS_F32 needs the DBR reduction: MSP_REDUCE_SEQ reproduces PETSc's f64 "
+                                "sums bit for bit, which a rounded basis cannot");
+    return MSP_ERR_SUP;
+  }
   int rc = mspi_set_device(k->ctx);
   if (!rc) rc = msp_ksp_set_up(k);
   if (!rc) rc = ensure_w(k);
@@ -396,8 +487,9 @@ int msp_ksp_solve(msp_ksp *k, const msp_vec *b, msp_vec *x) {
   int cycle_zero_guess = guess_zero, itcount = 0, its = 0, reason = 0;
   while (!reason) {
     /* KSPInitialResidual: VV(0) = b - A x (VecCopy + VecAXPY(-1)), or b for a zero guess */
-    if (!cycle_zero_guess) rc = mspi_residual(k->A, b->d, x->d, VV(k, 0));
-    else rc = mspi_copy(c, VV(k, 0), b->d, k->n);
+    double *r0 = k->basis_prec == MSP_BASIS_F32 ? k->cur : VV(k, 0); /* f32: rounded into VV(0) by the cycle */
+    if (!cycle_zero_guess) rc = mspi_residual(k->A, b->d, x->d, r0);
+    else rc = mspi_copy(c, r0, b->d, k->n);
     if (rc) return rc;
     int K = k->o.max_it - its;
     if (K > k->o.restart) K = k->o.restart;

@@ -158,6 +158,19 @@ int mspi_maxpy_norm_basis(msp_ctx *ctx, const double *win, double *wout, int nv,
 int mspi_maxpy_accum_basis(msp_ctx *ctx, double *x, const int *nvdev, const double *base, int64_t stride,
                            const double *scale, int64_t n, const double *coef_dev, int nv_expected);
 int mspi_h2d_async(msp_ctx *ctx, void *dev, const void *host, size_t bytes);
+/* ---- MSP_BASIS_F32: the same steps over a basis stored as float (msplit_cb.hip), VV(j) = base + j*stride with its
+   value (double)VV(j)[i] * scale[j]; all arithmetic f64, DBR only.  rnd(v) = (double)(float)v. ---- */
+/* cur = rnd(r) (f64; may be r itself), v0 = the same as float, sumsq_dev[0] = sum rnd(r)^2 */
+int mspi_cb_round_store(msp_ctx *ctx, const double *r, double *cur, float *v0, int64_t n, double *sumsq_dev,
+                        const int *stop);
+int mspi_cb_mdot(msp_ctx *ctx, const double *w, int nv, const float *base, int64_t stride, const double *scale,
+                 int64_t n, double *out_dev, const int *stop);
+/* s = rnd(win - sum_j h_j VV(j)) stored to vout (float) and cur (f64), ||s||^2, then mspi_gm_norm_update */
+int mspi_cb_maxpy_norm_update(msp_ctx *ctx, const double *win, double *cur, float *vout, int nv, const float *base,
+                              int64_t stride, const double *scale, int64_t n, mspi_gmres_dev g, int m,
+                              const int *stop);
+int mspi_cb_accum(msp_ctx *ctx, double *x, const int *nvdev, const float *base, int64_t stride, const double *scale,
+                  int64_t n, const double *coef_dev, int nv_expected);
 /* ---- the GMRES step's MatMult inside the CGS kernels (A in DV storage, 8-code ELL layout) ---- */
 int mspi_op_fusable(const msp_mat *A);
 /* h(0..nv-1) = (A (sdev[0] x)) . scale_j VV(j): stage 1 computes each row of A(sc x) in registers */

@@ -191,4 +191,20 @@ int msk_stencil_spmv(int dim, int32_t nx, int32_t ny, int32_t nz, int64_t nrows,
 int msk_box_stencil(int dim, int32_t nx, int32_t ny, int32_t nz, int64_t nrows, int lo, int hi, const BoxCoef* cf,
                     int32_t* rowptr, int32_t* col, double* val, hipStream_t s);
 int msk_blas1(int op, double* y, const double* x, const double* z, double alpha, int64_t n, hipStream_t s);
+// ---- compressed-basis GMRES (msplit_cb.hip): the Krylov basis in HBM as float, VV(j) = vb + j*stride (stride a
+// multiple of 1024), its value (double)VV(j)[i] * scale[j]; all arithmetic f64, DBR lane map and order.
+#define MSK_CB_MAX_GROUP 32
+// cur = rnd(r) as f64 (may be r itself), v0 = the same as f32, partial[c] = DBR partials of sum rnd(r)^2
+int msk_cb_round_store(const double* r, double* cur, float* v0, int64_t n, double* partial, const int* stop,
+                       hipStream_t s);
+// DBR stage 1 of w . VV(v), v < nv <= MSK_CB_MAX_GROUP, into partial[v * nchunks + c]
+int msk_cb_mdot(const double* w, const float* vb, int64_t stride, const double* scale, int nv, int64_t n,
+                double* partial, int64_t nchunks, const int* stop, hipStream_t s);
+// s = rnd(win - sum_j adev_j VV(j)) (PETSc grouping, any nv >= 1) to vout (f32) and cur (f64); partials of sum s^2
+int msk_cb_maxpy_norm(const double* win, double* cur, float* vout, const float* vb, int64_t stride,
+                      const double* scale, const double* adev, int nv, int64_t n, double* partial, const int* stop,
+                      hipStream_t s);
+// x = x + (0 + sum_j coef_j VV(j)), j < *nvdev
+int msk_cb_accum(double* x, const int* nvdev, const float* vb, int64_t stride, const double* scale,
+                 const double* coef, int64_t n, const int* stop, hipStream_t s);
 }

@@ -412,6 +412,70 @@ extern "C" int mspi_maxpy_accum_basis(msp_ctx* c, double* x, const int* nvdev, c
   return MSP_SUCCESS;
 }
 
+// ---- MSP_BASIS_F32 (msplit_cb.hip): the same four steps over a float basis.  Byte counts: 4 per basis element,
+// 8 per element of the f64 vectors (W, the current vector, x).  The MSPLIT_TUNING variants of the f64 MDot / MAXPY
+// do not apply: each step has one kernel.
+extern "C" int mspi_cb_round_store(msp_ctx* c, const double* r, double* cur, float* v0, int64_t n, double* sumsq_dev,
+                                   const int* stop) {
+  const int64_t nch = nchunks_of(n);
+  if (nch == 0) {
+    HIPCHK(hipMemsetAsync(sumsq_dev, 0, sizeof(double), c->stream));
+    return MSP_SUCCESS;
+  }
+  int rc = ensure_partial(c, nch * MSPI_MAX_GROUP);
+  if (rc) return rc;
+  KTimer kt(c, MSP_KERNEL_NORM, (8.0 + 8.0 + 4.0) * (double)n);  // r read, cur and VV(0) written
+  KCHK(msk_cb_round_store(r, cur, v0, n, c->partial, stop, c->stream));
+  KCHK(msk_dot_stage2(c->partial, nch, 1, sumsq_dev, stop, c->stream));
+  return MSP_SUCCESS;
+}
+
+extern "C" int mspi_cb_mdot(msp_ctx* c, const double* w, int nv, const float* base, int64_t stride,
+                            const double* scale, int64_t n, double* out_dev, const int* stop) {
+  if (nv <= 0) return MSP_SUCCESS;
+  const int64_t nch = nchunks_of(n);
+  if (nch == 0) {
+    HIPCHK(hipMemsetAsync(out_dev, 0, (size_t)nv * sizeof(double), c->stream));
+    return MSP_SUCCESS;
+  }
+  int rc = ensure_partial(c, nch * MSPI_MAX_GROUP);
+  if (rc) return rc;
+  const int ng = (nv + MSPI_MAX_GROUP - 1) / MSPI_MAX_GROUP;  // W is read once per launch
+  KTimer kt(c, MSP_KERNEL_MDOT, (double)n * (4.0 * nv + 8.0 * ng));
+  for (int g0 = 0; g0 < nv; g0 += MSPI_MAX_GROUP) {
+    const int g = std::min(MSPI_MAX_GROUP, nv - g0);
+    KCHK(msk_cb_mdot(w, base + (int64_t)g0 * stride, stride, scale + g0, g, n, c->partial, nch, stop, c->stream));
+    KCHK(msk_dot_stage2(c->partial, nch, g, out_dev + g0, stop, c->stream));
+  }
+  return MSP_SUCCESS;
+}
+
+extern "C" int mspi_cb_maxpy_norm_update(msp_ctx* c, const double* win, double* cur, float* vout, int nv,
+                                         const float* base, int64_t stride, const double* scale, int64_t n,
+                                         mspi_gmres_dev g, int m, const int* stop) {
+  const int64_t nch = nchunks_of(n);
+  if (nch == 0 || nv <= 0) {
+    mspi_set_error(MSP_ERR_ARG_SIZ, "maxpy_norm on an empty basis");
+    return MSP_ERR_ARG_SIZ;
+  }
+  int rc = ensure_partial(c, nch * MSPI_MAX_GROUP);
+  if (rc) return rc;
+  {
+    // W read, nv basis vectors read, VV(it+1) (4 B) and the current vector (8 B) written
+    KTimer kt(c, MSP_KERNEL_MAXPY, (double)n * (8.0 + 4.0 * nv + 4.0 + 8.0));
+    KCHK(msk_cb_maxpy_norm(win, cur, vout, base, stride, scale, g.h, nv, n, c->partial, stop, c->stream));
+  }
+  return mspi_gm_norm_update(c, g, c->partial, nch, m);
+}
+
+extern "C" int mspi_cb_accum(msp_ctx* c, double* x, const int* nvdev, const float* base, int64_t stride,
+                             const double* scale, int64_t n, const double* coef_dev, int nv_expected) {
+  if (n <= 0) return MSP_SUCCESS;
+  KTimer kt(c, MSP_KERNEL_MAXPY, (double)n * (4.0 * nv_expected + 16.0));
+  KCHK(msk_cb_accum(x, nvdev, base, stride, scale, coef_dev, n, nullptr, c->stream));
+  return MSP_SUCCESS;
+}
+
 
 extern "C" int mspi_scale(msp_ctx* c, double* x, int64_t n, double alpha) {
   KTimer kt(c, MSP_KERNEL_SCALE, 16.0 * (double)n);

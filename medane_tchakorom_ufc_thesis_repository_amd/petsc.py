@@ -20,6 +20,7 @@ from ._lib import KspOpts, LsqrOpts, MsplitError, call
 
 PETSC_ERR_SUP = 56
 PETSC_ERR_ARG_WRONG = 62
+PETSC_ERR_ARG_OUTOFRANGE = 63
 
 
 def _dp(a: np.ndarray):
@@ -727,6 +728,28 @@ class KSP:
     def gmres_set_restart(self, m: int):                            # KSPGMRESSetRestart
         self._set(restart=int(m))
 
+    # storage precision of the Krylov basis (msp_ksp_set_basis_precision): "single" keeps the basis in HBM as
+    # float with all arithmetic in double -- half the basis bytes per step and per block
+    BASIS_PRECISIONS = {"double": 0, "single": 1}
+
+    def set_basis_precision(self, precision: str):
+        word = str(precision).lower()
+        if word not in self.BASIS_PRECISIONS:
+            raise MsplitError(PETSC_ERR_ARG_OUTOFRANGE,
+                              f"basis precision {precision!r}: expected one of {sorted(self.BASIS_PRECISIONS)}")
+        call("msp_ksp_set_basis_precision", self.h, self.BASIS_PRECISIONS[word])
+
+    def get_basis_precision(self) -> str:
+        v = C.c_int()
+        call("msp_ksp_get_basis_precision", self.h, C.byref(v))
+        return {n: w for w, n in self.BASIS_PRECISIONS.items()}[v.value]
+
+    def get_work_bytes(self) -> int:
+        """Device bytes held after set-up and the first solve: basis, W / current vector, recurrence block."""
+        v = C.c_int64()
+        call("msp_ksp_get_work_bytes", self.h, C.byref(v))
+        return v.value
+
     def set_from_options(self, opts: Options):                      # KSPSetFromOptions
         p = self.prefix
         kt = opts.get_string("ksp_type", "gmres", p)
@@ -756,6 +779,12 @@ class KSP:
         if opts.has("ksp_initial_guess_nonzero", p):
             o.guess_nonzero = 1 if opts.get_bool("ksp_initial_guess_nonzero", False, p) else 0
         call("msp_ksp_set_opts", self.h, C.byref(o))
+        if opts.has("msplit_basis_precision", p):
+            word = opts.get_string("msplit_basis_precision", "double", p)
+            if str(word).lower() not in self.BASIS_PRECISIONS:
+                raise MsplitError(PETSC_ERR_ARG_OUTOFRANGE, f"-{p}msplit_basis_precision {word}: expected one of "
+                                                            f"{sorted(self.BASIS_PRECISIONS)}")
+            self.set_basis_precision(word)
 
     def set_up(self):
         call("msp_ksp_set_up", self.h)

@@ -13,12 +13,16 @@ typedef struct {
   PetscInt restart;
   PetscReal haptol, breakdowntol;
   PetscInt reduction; /* -msplit_reduction dbr|seq on this KSP's prefix; -1: the shared context's order */
+  PetscInt basis_precision; /* -msplit_basis_precision double|single: MSP_BASIS_F64 / MSP_BASIS_F32 */
 } KSP_MSplit;
 
 /* -msplit_reduction: the device reduction order (include/msplit.h msp_ctx_set_reduction).  "seq" is
  * the parity mode -- every dot, norm and MDot summed in PETSc's Seq order, so iteration counts and
  * residual histories are the reference's bit for bit -- at a fraction of the speed (bench.py seq_mode). */
 static const char *const MSplitReductions[] = {"dbr", "seq", "MSplitReduction", "MSPLIT_REDUCTION_", NULL};
+/* -msplit_basis_precision: the Krylov basis stored in HBM as double, or as float with all arithmetic in double
+ * (include/msplit.h msp_ksp_set_basis_precision); single excludes -msplit_reduction seq */
+static const char *const MSplitBasisPrecisions[] = {"double", "single", "MSplitBasisPrecision", "MSPLIT_BASIS_", NULL};
 
 #define MSPCall(e) do { int _rc = (e); PetscCheck(!_rc, PETSC_COMM_SELF, _rc, "%s", msp_get_last_error()); } while (0)
 
@@ -226,6 +230,7 @@ static PetscErrorCode KSPSolve_MSplitGMRES_Body(KSP ksp)
   o.uirnorm       = cctx ? (int32_t)cctx->initialrtol : 0;   /* KSPConvergedDefaultSetUIRNorm */
   o.guess_nonzero = ksp->guess_zero ? 0 : 1;
   MSPCall(msp_ksp_set_opts(ms->ksp, &o));
+  MSPCall(msp_ksp_set_basis_precision(ms->ksp, (int)ms->basis_precision));
   PetscCall(VecGetLocalSize(ksp->vec_rhs, &n));
   PetscCall(VecGetArrayRead(ksp->vec_rhs, &b));
   MSPCall(msp_vec_set_values(ms->b, 0, n, b));
@@ -260,6 +265,10 @@ static PetscErrorCode KSPSetFromOptions_MSplitGMRES(KSP ksp, PetscOptionItems *P
   PetscCall(PetscOptionsInt("-ksp_gmres_restart", "Krylov directions", NULL, ms->restart, &ms->restart, NULL));
   PetscCall(PetscOptionsReal("-ksp_gmres_haptol", "happy breakdown tolerance", NULL, ms->haptol, &ms->haptol, NULL));
   PetscCall(MSplitSetFromOptionsReduction(PetscOptionsObject, &ms->reduction));
+  PetscEnum bp = (PetscEnum)ms->basis_precision;
+  PetscCall(PetscOptionsEnum("-msplit_basis_precision", "storage precision of the Krylov basis", NULL,
+                             MSplitBasisPrecisions, bp, &bp, NULL));
+  ms->basis_precision = (PetscInt)bp;
   PetscCall(PetscOptionsReal("-ksp_gmres_breakdown_tolerance", "restart breakdown tolerance", NULL, ms->breakdowntol,
                              &ms->breakdowntol, NULL));
   PetscOptionsHeadEnd();

@@ -1,0 +1,280 @@
+"""Compressed-basis GMRES (-msplit_basis_precision single, MSP_BASIS_F32) on the GPU.
+
+The Krylov basis is stored in HBM as float and every other number stays double, so the device solve is held to the
+Python twin with the f32 rounding (tests/basis_twin.py) bit for bit: iteration count, reason, residual norm, every
+history entry and x.  The shapes are the smallest that reach each path of the four kernels (msplit_cb.hip): a
+partial chunk only, odd n, one full chunk plus a tail, two full chunks plus a tail, more than 32 vectors, GMRES(1),
+many restarts; every SpMV route feeds the same step; f32 subnormals and overflow behave as numpy's conversion.
+"""
+import os
+
+import numpy as np
+import pytest
+
+import basis_twin as bt
+from medane_tchakorom_ufc_thesis_repository_amd import MsplitError
+from medane_tchakorom_ufc_thesis_repository_amd.comm import LocalComm
+from medane_tchakorom_ufc_thesis_repository_amd.multisplitting import make_blocks, sm_solve
+from medane_tchakorom_ufc_thesis_repository_amd.petsc import KSP, Mat, Options, Vec
+from test_gpu_gmres import _opts_str, _random_csr
+
+pytestmark = pytest.mark.gpu
+
+SINGLE = " -msplit_basis_precision single"
+
+
+def _solve_on(ksp, ctx, A, b, x0):
+    bv = Vec.from_array(ctx, b)
+    xv = Vec.from_array(ctx, x0) if x0 is not None else Vec(ctx, A.shape[0])
+    ksp.solve(bv, xv)
+    return xv.get_array(), {"its": ksp.get_iteration_number(), "reason": ksp.get_converged_reason(),
+                            "rnorm": ksp.get_residual_norm(), "hist": ksp.get_residual_history()}
+
+
+def _gpu(ctx, A, b, x0, optstr):
+    ksp = KSP(ctx)
+    ksp.set_operators(A)
+    ksp.set_from_options(Options(optstr))
+    return _solve_on(ksp, ctx, A, b, x0)
+
+
+def _same(got, want):
+    (xg, rg), (xw, rw) = got, want
+    assert (rg["its"], rg["reason"]) == (rw["its"], rw["reason"])
+    assert rg["rnorm"] == rw["rnorm"]
+    assert np.array_equal(rg["hist"], rw["hist"], equal_nan=True)
+    assert np.array_equal(xg, xw, equal_nan=True)
+
+
+def _kw(o, nonzero):
+    return dict(o, guess_nonzero=1 if nonzero else 0)
+
+
+# (dim, sizes, options, nonzero guess)
+BOX_CASES = {
+    "restart40": (3, (9, 8, 7), dict(restart=40, max_it=200, rtol=1e-10), False),       # > 32 vectors, BuildSoln split
+    "odd_n": (3, (13, 11, 7), dict(restart=5, max_it=57, rtol=1e-30), True),            # n = 1001, many restarts
+    "chunk_tail": (3, (17, 16, 16), dict(restart=30, max_it=300, rtol=1e-4), False),    # n = 4352: one chunk + tail
+    "two_chunks": (3, (16, 16, 33), dict(restart=30, max_it=300, rtol=1e-10), False),   # n = 8448: two chunks + tail
+    "gmres1": (3, (10, 10, 10), dict(restart=1, max_it=25, rtol=1e-30), True),
+    "inner2d": (2, (33, 40, 1), dict(restart=30, max_it=20, rtol=1e-20, uirnorm=1), True),  # C1/C3 inner options
+}
+
+
+def _box(ctx, oracle, dim, nx, ny, nz):
+    if dim == 3:
+        return oracle.poisson3d_rows(nx, ny, nz, 0, nz), Mat.box_stencil(ctx, 3, nx, ny, nz)
+    return oracle.poisson2d_rows(nx, ny, 0, nx * ny), Mat.box_stencil(ctx, 2, ny, nx)
+
+
+def _box_problem(ctx, oracle, name):
+    dim, (nx, ny, nz), o, nonzero = BOX_CASES[name]
+    O, A = _box(ctx, oracle, dim, nx, ny, nz)
+    n = O.shape[0]
+    b = O.mult(np.ones(n))
+    x0 = np.random.default_rng(7).uniform(-1, 1, n) if nonzero else None
+    return O, A, b, x0, o, nonzero
+
+
+_twins = {}
+
+
+def _twin(name, O, b, x0, o, nonzero):
+    """The f32 twin's solve of a named case, computed once and shared (never modified)."""
+    if name not in _twins:
+        _twins[name] = bt.gmres(O, b, x0=x0, rnd=bt.f32, **_kw(o, nonzero))
+    return _twins[name]
+
+
+@pytest.mark.parametrize("name", list(BOX_CASES))
+def test_box_dv_bitwise_vs_f32_twin(ctx, oracle, name):
+    O, A, b, x0, o, nonzero = _box_problem(ctx, oracle, name)
+    A.set_storage("dv")
+    want = _twin(name, O, b, x0, o, nonzero)
+    _same(_gpu(ctx, A, b, x0, _opts_str(o, nonzero) + SINGLE), want)
+    # the mode is really on: the f64 solve of the same system is another computation
+    x64, _ = oracle.gmres(O, b, x0=x0, reduce_mode=oracle.REDUCE_DBR, **_kw(o, nonzero))
+    assert not np.array_equal(want[0], x64)
+
+
+@pytest.mark.parametrize("route", ["csr", "matfree", "convdiff", "random_csr"])
+def test_every_spmv_route_bitwise_vs_f32_twin(ctx, oracle, route):
+    """The step's MatMult is the operator's own scaled product on the f64 current vector, whatever the storage."""
+    nx, ny, nz = 17, 16, 16
+    o, nonzero = dict(restart=30, max_it=300, rtol=1e-4), False
+    if route == "csr":
+        O, A = _box(ctx, oracle, 3, nx, ny, nz)
+        A.set_storage("csr")
+        assert A.get_storage() == "csr"
+    elif route == "matfree":
+        O = oracle.poisson3d_rows(nx, ny, nz, 0, nz)
+        A = Mat.box_matfree(ctx, 3, nx, ny, nz)
+    elif route == "convdiff":
+        P = (0.5, -0.25, 0.125)
+        O = oracle.convdiff_rows(3, nx, ny, nz, 0, nx * ny * nz, P)
+        A = Mat.box_convdiff(ctx, 3, nx, ny, nz, False, False, P)
+    else:   # nonsymmetric, no stencil: seeded random off-diagonal pattern under a dominant diagonal
+        n = 5000
+        rp, c, v = _random_csr(np.random.default_rng(2024), n, 8)
+        O = oracle.Mat.from_arrays(n, n, rp, c, v)
+        A = Mat.from_csr(ctx, n, n, rp, c, v)
+        o = dict(restart=30, max_it=60, rtol=1e-8)
+    n = O.shape[0]
+    b = O.mult(np.ones(n)) if route != "random_csr" else np.random.default_rng(5).uniform(-1, 1, n)
+    key = "chunk_tail" if route in ("csr", "matfree") else route   # the same system as the DV case
+    _same(_gpu(ctx, A, b, None, _opts_str(o, nonzero) + SINGLE), _twin(key, O, b, None, o, nonzero))
+
+
+@pytest.mark.parametrize("exp", [-125, -140])
+def test_tiny_residual_keeps_f32_subnormals(ctx, oracle, exp):
+    """b = A 1 scaled by 2^exp on 9x8x7.  At 2^-125 the entries of VV(0) (1, 2 or 3 times 2^-125) are the smallest
+    f32 normals and the restart residuals below them are subnormal; at 2^-140 VV(0) itself is subnormal in f32
+    (exactly representable: a conversion that flushed to zero would end the solve at once with a zero residual)."""
+    O, A = _box(ctx, oracle, 3, 9, 8, 7)
+    A.set_storage("dv")
+    b = O.mult(np.ones(O.shape[0])) * 2.0 ** exp
+    o = dict(restart=30, max_it=200, rtol=1e-10)
+    want = bt.gmres(O, b, rnd=bt.f32, **o)
+    assert want[1]["its"] > 0 and want[1]["hist"][0] > 0.0
+    if exp == -140:
+        s0 = b.astype(np.float32)
+        assert np.all(np.abs(s0[s0 != 0]) < np.finfo(np.float32).tiny)
+    _same(_gpu(ctx, A, b, None, _opts_str(o, False) + SINGLE), want)
+
+
+def test_entries_beyond_f32_range_diverge_nanorinf(ctx, oracle):
+    O, A = _box(ctx, oracle, 3, 9, 8, 7)
+    A.set_storage("dv")
+    b = O.mult(np.ones(O.shape[0])) * 1e39
+    o = dict(restart=30, max_it=200, rtol=1e-10)
+    want = bt.gmres(O, b, rnd=bt.f32, **o)
+    assert want[1]["reason"] == bt.DIVERGED_NANORINF
+    _same(_gpu(ctx, A, b, None, _opts_str(o, False) + SINGLE), want)
+    # the f64 basis takes the same right-hand side in its stride
+    _same(_gpu(ctx, A, b, None, _opts_str(o, False)), oracle.gmres(O, b, reduce_mode=oracle.REDUCE_DBR, **o))
+
+
+def test_graph_replay_equals_eager(ctx, oracle):
+    """MSPLIT_GRAPHS=0 and the default give the same bits; the second solve on one KSP replays the captured cycles."""
+    O, A, b, x0, o, nonzero = _box_problem(ctx, oracle, "chunk_tail")
+    A.set_storage("dv")
+    want = _twin("chunk_tail", O, b, x0, o, nonzero)
+
+    def twice(graphs):
+        os.environ["MSPLIT_GRAPHS"] = "1" if graphs else "0"
+        try:
+            ksp = KSP(ctx)
+            ksp.set_operators(A)
+            ksp.set_from_options(Options(_opts_str(o, nonzero) + SINGLE))
+            bv, xv = Vec.from_array(ctx, b), Vec(ctx, A.shape[0])
+            out = []
+            for _ in range(2):
+                ksp.solve(bv, xv)
+                out.append((xv.get_array(), {"its": ksp.get_iteration_number(), "reason": ksp.get_converged_reason(),
+                                             "rnorm": ksp.get_residual_norm(), "hist": ksp.get_residual_history()}))
+            return out
+        finally:
+            os.environ.pop("MSPLIT_GRAPHS", None)
+
+    for got in twice(False) + twice(True):
+        _same(got, want)
+
+
+def test_default_is_the_f64_basis(ctx, oracle):
+    O, A, b, x0, o, nonzero = _box_problem(ctx, oracle, "chunk_tail")
+    want = oracle.gmres(O, b, x0=x0, reduce_mode=oracle.REDUCE_DBR, **_kw(o, nonzero))
+    for extra in ("", " -msplit_basis_precision double"):
+        ksp = KSP(ctx)
+        ksp.set_operators(A)
+        ksp.set_from_options(Options(_opts_str(o, nonzero) + extra))
+        assert ksp.get_basis_precision() == "double"
+        _same(_solve_on(ksp, ctx, A, b, x0), want)
+
+
+def test_switching_precision_on_one_ksp(ctx, oracle):
+    O, A, b, x0, o, nonzero = _box_problem(ctx, oracle, "chunk_tail")
+    w32 = _twin("chunk_tail", O, b, x0, o, nonzero)
+    w64 = oracle.gmres(O, b, x0=x0, reduce_mode=oracle.REDUCE_DBR, **_kw(o, nonzero))
+    ksp = KSP(ctx)
+    ksp.set_operators(A)
+    ksp.set_from_options(Options(_opts_str(o, nonzero)))
+    for word, want in (("single", w32), ("double", w64), ("single", w32)):
+        ksp.set_basis_precision(word)
+        assert ksp.get_basis_precision() == word
+        _same(_solve_on(ksp, ctx, A, b, x0), want)
+
+
+def test_seq_reduction_excludes_single(ctx, oracle):
+    O, A, b, x0, o, nonzero = _box_problem(ctx, oracle, "restart40")
+    ksp = KSP(ctx)
+    ksp.set_operators(A)
+    ksp.set_from_options(Options(_opts_str(o, nonzero) + SINGLE))
+    before = ctx.get_reduction()
+    ctx.set_reduction("seq")
+    try:
+        with pytest.raises(MsplitError) as e:
+            _solve_on(ksp, ctx, A, b, x0)
+        assert e.value.code == 56   # PETSC_ERR_SUP
+    finally:
+        ctx.set_reduction(before)
+    assert ctx.get_reduction() == before == "dbr"
+    _same(_solve_on(ksp, ctx, A, b, x0), _twin("restart40", O, b, x0, o, nonzero))   # and the KSP still serves
+
+
+def test_bad_precision_word_raises(ctx):
+    import ctypes as C
+    from medane_tchakorom_ufc_thesis_repository_amd import _lib
+    ksp = KSP(ctx)
+    with pytest.raises(MsplitError):
+        ksp.set_from_options(Options("-msplit_basis_precision half"))
+    with pytest.raises(MsplitError):
+        ksp.set_basis_precision("half")
+    assert _lib.load().msp_ksp_set_basis_precision(ksp.h, C.c_int(7)) == 63   # MSP_ERR_ARG_OUTOFRANGE
+    assert ksp.get_basis_precision() == "double"
+
+
+def test_work_bytes_single_at_most_0p6_of_double(ctx):
+    """64^3, GMRES(30): 31 basis vectors.  double: 8*31 B/row (the W-free step holds no W); single: 4*31 B/row plus
+    W and the current vector, (4*31 + 16) / (8*31) = 0.565; the margin to 0.6 covers the recurrence block and the
+    4 KiB paddings."""
+    A = Mat.box_stencil(ctx, 3, 64, 64, 64)
+    n = A.shape[0]
+    b = Vec.from_array(ctx, np.ones(n))
+    got = {}
+    for word in ("double", "single"):
+        ksp = KSP(ctx)
+        ksp.set_operators(A)
+        ksp.set_from_options(Options(f"-ksp_gmres_restart 30 -ksp_max_it 40 -ksp_rtol 1e-2 "
+                                     f"-msplit_basis_precision {word}"))
+        assert ksp.get_work_bytes() == 0
+        ksp.solve(b, Vec(ctx, n))
+        got[word] = ksp.get_work_bytes()
+    print(f"work bytes at 64^3, GMRES(30): double {got['double']}, single {got['single']}, "
+          f"ratio {got['single'] / got['double']:.4f}")
+    assert got["double"] >= 8 * 31 * n
+    assert got["single"] <= 0.6 * got["double"]
+
+
+def test_sm_driver_with_single_precision_inner_solves(ctx):
+    """sm_solve, 3D 12x10x8 in two blocks, the inner GMRES(30)s (max_it 20, as the campaign's) on a float basis: the
+    driver stops by its own f64 residual test, a rerun gives the same bits, and the inner solves are not the f64
+    ones.  (A driver twin is out of scope: the inner solve is pinned above.)"""
+    rtol, nb = 1e-6, 2
+
+    def run(word):
+        opts = Options(" ".join(f"-inner{k + 1}_ksp_max_it 20 -inner{k + 1}_ksp_rtol 1e-20 -inner{k + 1}_pc_type none "
+                                f"-inner{k + 1}_msplit_basis_precision {word}" for k in range(nb)))
+        comm = LocalComm()
+        blocks = make_blocks(ctx, 3, 12, 10, 8, nb, range(nb), opts, comm)
+        assert all(blk.ksp.get_basis_precision() == word for blk in blocks)
+        res = sm_solve(blocks, comm, rtol=rtol, max_outer=200)
+        return res, np.concatenate([blk.x.get_array() for blk in blocks])
+
+    r1, x1 = run("single")
+    r2, x2 = run("single")
+    rd, xd = run("double")
+    print(f"sm_solve 12x10x8 nb=2: outer iterations single {r1.outer_its}, double {rd.outer_its}")
+    assert r1.outer_its < 200 and r1.hist[-1] <= rtol * r1.norm0    # stopped by the driver's f64 residual test
+    assert r1.outer_its == r2.outer_its and np.array_equal(np.array(r1.hist), np.array(r2.hist))
+    assert np.array_equal(np.array(r1.inner_its), np.array(r2.inner_its)) and np.array_equal(x1, x2)
+    assert not np.array_equal(x1, xd)
