@@ -547,7 +547,8 @@ int msd_smsm_global_solve(msp_ctx *ctx, const msd_problem *p, const msd_options 
   for (int i = 0; i < R.nlocal; ++i) {
     msd_block *B = R.blk[i];
     CK(msp_dense_create(ctx, B->lo + B->n + B->hi, p->s, &B->S));
-    CK(msp_dense_create(ctx, B->n, p->s, &B->R));
+    /* -msplit_minimization_precision single: R = A S stored as float (MSP_DENSE_F32); S stays double */
+    CK(msp_dense_create_prec(ctx, B->n, p->s, p->r_f32 ? MSP_DENSE_F32 : MSP_DENSE_F64, &B->R));
     Rs[i] = B->R;
     bs[i] = B->b;
   }
@@ -732,7 +733,7 @@ int msd_am_solve(msp_ctx *ctx, const msd_problem *p, const msd_options *o, const
 static int amam_setup_block(msp_ctx *ctx, const msd_problem *p, const msd_options *o, msd_block *B) {
   const msd_layout *L = &B->L;
   CK(msp_dense_create(ctx, B->lo + B->n + B->hi, p->s, &B->S));
-  CK(msp_dense_create(ctx, B->n, p->s, &B->R));
+  CK(msp_dense_create_prec(ctx, B->n, p->s, p->r_f32 ? MSP_DENSE_F32 : MSP_DENSE_F64, &B->R));
   char prefix[32];
   snprintf(prefix, sizeof(prefix), "outer%d_", L->b + 1);
   B->rtr = p->rtr;
@@ -765,7 +766,8 @@ static int amam_setup_block(msp_ctx *ctx, const msd_problem *p, const msd_option
     msd_layout Lj;
     CK(msd_layout_make(p->dim, p->nx, p->ny, p->nz, p->nb, j, p->peclet, &Lj));
     const int64_t nj = Lj.r1 - Lj.r0, loj = Lj.has_lo ? Lj.plane : 0, hij = Lj.has_hi ? Lj.plane : 0;
-    CK(msp_dense_create(ctx, nj, p->s, &B->Rrep[j]));
+    /* the replicated rows of R take R's precision (the Gram parts and Gsum above stay double) */
+    CK(msp_dense_create_prec(ctx, nj, p->s, p->r_f32 ? MSP_DENSE_F32 : MSP_DENSE_F64, &B->Rrep[j]));
     CK(msp_dense_zero_entries(B->Rrep[j]));
     /* b_j = A_block_j 1 (utils.c:623-650) */
     msp_mat *Aj;
@@ -854,7 +856,8 @@ int msd_amam_global_solve(msp_ctx *ctx, const msd_problem *p, const msd_options 
   for (int j = 0; j < p->nb && !p->rtr; ++j) {
     msd_layout Lj;
     CK(msd_layout_make(p->dim, p->nx, p->ny, p->nz, p->nb, j, p->peclet, &Lj));
-    const int64_t c = (Lj.r1 - Lj.r0) * (int64_t)p->s;
+    int64_t c = (Lj.r1 - Lj.r0) * (int64_t)p->s;
+    if (p->r_f32) c = (c + 1) / 2; /* cap counts doubles: two floats of a single-precision R fill one */
     if (c > cap) cap = c;
   }
   char name[128], rname[136];

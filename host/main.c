@@ -19,6 +19,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <strings.h>
 
 #include "msplit_drivers.h"
 
@@ -46,7 +47,7 @@ static int usage(void) {
                   "synchronous-multisplitting-synchronous-minimization-global | asynchronous-multisplitting | "
                   "asynchronous-multisplitting-asynchronous-minimization-global> "
                   "-m M -n N [-s S] [-rtol R] [-dim 3 -p P] [-peclet px,py,pz] [-nb B] [-msplit_reduction dbr|seq] [-msplit_minimization lsqr|rtr] "
-                  "[-innerK_msplit_basis_precision double|single] [-json] ...\n");
+                  "[-msplit_minimization_precision double|single] [-innerK_msplit_basis_precision double|single] [-json] ...\n");
   return 2;
 }
 
@@ -82,6 +83,12 @@ int main(int argc, char **argv) {
   const char *mini = msd_opt_str(o, NULL, "msplit_minimization", "lsqr");
   if (strcmp(mini, "lsqr") && strcmp(mini, "rtr")) return usage();
   p.rtr = !strcmp(mini, "rtr");
+  const char *mprec = msd_opt_str(o, NULL, "msplit_minimization_precision", "double");
+  if (strcasecmp(mprec, "double") && strcasecmp(mprec, "single")) {
+    fprintf(stderr, "-msplit_minimization_precision %s: expected double or single\n", mprec);
+    return usage();
+  }
+  p.r_f32 = !strcasecmp(mprec, "single");
   const char *pe = msd_opt_str(o, NULL, "peclet", NULL);
   if (pe && sscanf(pe, "%lf,%lf,%lf", &p.peclet[0], &p.peclet[1], &p.peclet[2]) != 3) return usage();
   if (msd_opt_int(o, NULL, "npb", 1) != 1) {

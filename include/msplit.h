@@ -309,6 +309,27 @@ int msp_ksp_get_work_bytes(const msp_ksp *ksp, int64_t *bytes);
  * most recent multisplitting iterates, one per column) and R = A S this way;
  * each GPU keeps only its own rows (plus, for S, the neighbour planes R needs). */
 int msp_dense_create(msp_ctx *ctx, int64_t nrows, int32_t ncols, msp_dense **A);   /* zero entries */
+/* Storage precision of a dense block (-msplit_minimization_precision double|single).  No reference counterpart;
+ * the block is create_matrix_dense's (utils.c:123-137).
+ * MSP_DENSE_F64 (msp_dense_create): column-major doubles.
+ * MSP_DENSE_F32: the compressed R = A S of the minimization: column-major floats, lda (in elements) a multiple of
+ * 1024, so columns stay 4 KiB aligned.  Each entry is rounded to float once, when it is stored (round to nearest
+ * even, gradual underflow, overflow to +-inf: the rule of msp_ksp_set_basis_precision), and promoted to double as
+ * it is read; every sum, the LSQR scalars and vectors and the operator stay double, in the order they have over a
+ * double block.  Accepted by set_values / set_column (rounding on the device), get_values (the promoted
+ * doubles), zero_entries, create_view (the view keeps the precision), msp_dense_mult, msp_dense_mult_transpose,
+ * msp_lsqr_set_operators (blocks of either precision, per block), msp_dense_gram (as R) and
+ * msp_mat_matmult_dense (as R: the f64 row sum rounded once at the store).  S, Gc and msp_dense_sum stay double.
+ * DBR reduction only: under MSP_REDUCE_SEQ a sum over an F32 block returns MSP_ERR_SUP.
+ * Any other prec: MSP_ERR_ARG_OUTOFRANGE. */
+#define MSP_DENSE_F64 0
+#define MSP_DENSE_F32 1
+int msp_dense_create_prec(msp_ctx *ctx, int64_t nrows, int32_t ncols, int prec, msp_dense **A); /* zero entries */
+/* The block's storage precision (no reference counterpart; the block: utils.c:123-137). */
+int msp_dense_get_precision(const msp_dense *A, int *prec);
+/* MatDenseGetArray of an MSP_DENSE_F32 block (utils.c:123-137 for the block); MSP_ERR_SUP on an F64 block, as
+ * msp_dense_get_array is on an F32 one. */
+int msp_dense_get_array_f32(msp_dense *A, float **device_ptr);
 int msp_dense_destroy(msp_dense **A);
 int msp_dense_get_info(const msp_dense *A, int64_t *nrows, int32_t *ncols, int64_t *lda);
 int msp_dense_get_array(msp_dense *A, double **device_ptr);                        /* MatDenseGetArray */
@@ -344,7 +365,8 @@ int msp_dense_sum(int32_t nparts, const msp_dense *const *parts, msp_dense *out)
 int msp_dense_create_view(msp_dense *A, int32_t col0, int32_t ncols, msp_dense **view);
 /* R = A S -- MatMatMult(A_block_jacobi_resdistributed, S, MAT_REUSE_MATRIX, R)
  * (SMSM-global.c:325-327): A is nrows(R) x nrows(S), R and S have the same
- * column count.  Per row of A and column of S: ascending columns, from 0. */
+ * column count.  Per row of A and column of S: ascending columns, from 0.
+ * S must be MSP_DENSE_F64 (else MSP_ERR_SUP); an MSP_DENSE_F32 R takes each f64 row sum rounded once. */
 int msp_mat_matmult_dense(msp_mat *A, const msp_dense *S, msp_dense *R);
 
 /* ------------------------------------------------------------------- comm */

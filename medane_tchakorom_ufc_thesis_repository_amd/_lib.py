@@ -120,6 +120,9 @@ _SIGS = {
     "msp_mat_release_csr": [_vp],
     "msp_mat_get_spmv_kernel": [_vp, _P(C.c_char_p)],
     "msp_dense_create": [_vp, C.c_int64, C.c_int32, _P(_vp)],
+    "msp_dense_create_prec": [_vp, C.c_int64, C.c_int32, C.c_int, _P(_vp)],
+    "msp_dense_get_precision": [_vp, _P(C.c_int)],
+    "msp_dense_get_array_f32": [_vp, _P(_vp)],
     "msp_dense_destroy": [_P(_vp)],
     "msp_dense_get_info": [_vp, _P(C.c_int64), _i32p, _P(C.c_int64)],
     "msp_dense_get_array": [_vp, _P(_vp)],

@@ -41,6 +41,7 @@ import time
 import uuid
 from dataclasses import dataclass, field
 
+from .multisplitting import slot_doubles
 from .petsc import AsyncBroadcast, AsyncMessages, ConvDetection
 
 
@@ -206,7 +207,7 @@ def am_solve(blocks, comm, rtol: float, atol: float = 1e-100, max_iterations: in
     if variant == "amam_global":                     # the largest block (of R, or Gram part) any block broadcasts
         cap = ordered[0].bcast_cap()
         if getattr(ordered[0], "minimization", "lsqr") == "lsqr":
-            cap = max(R.shape[0] * R.shape[1] for R in ordered[0].R_rep)
+            cap = max(slot_doubles(R) for R in ordered[0].R_rep)
     asyncs = {}
     owner_here = ordered[0].layout.b == 0
     if owner_here:                                   # block 0 creates the regions, the others open them

@@ -57,7 +57,8 @@ typedef struct {
   uint64_t version[2];      /* publish number of the payload each buffer holds */
   int64_t nrows[2], ncols[2];
   uint64_t published;       /* publishes so far (written by the source only) */
-  uint8_t pad[128 - 8 - 8 - 16 - 32 - 8];
+  int32_t esize[2];         /* bytes per element of the payload each buffer holds (8; 4: an MSP_DENSE_F32 block) */
+  uint8_t pad[128 - 8 - 8 - 16 - 32 - 8 - 8];
 } src_line;
 
 typedef struct {
@@ -83,7 +84,8 @@ typedef struct {
   _Atomic uint64_t claim; /* (count << 1) | buffer of the source's latest publish; == pub: nothing in flight */
   int64_t nrows[2], ncols[2];
   int32_t nbuf;           /* the source's device buffers (1 or 2) */
-  uint8_t pad[128 - 16 - 32 - 4];
+  int32_t esize[2];       /* bytes per element of the payload each buffer holds */
+  uint8_t pad[128 - 16 - 32 - 4 - 8];
 } abc_dline;
 
 #define ABC_MAX_DEVICE_RANKS 512 /* the reading words are nranks x 2 x nranks */
@@ -370,32 +372,41 @@ static int ensure_registered(msp_abcast *b) {
   return MSP_SUCCESS;
 }
 
-/* one payload of nrows x ncols, column j at src + j*ld, either in HBM (ctx != NULL) or host memory */
+/* one payload of nrows x ncols elements of esize bytes (8: doubles; 4: the floats of an MSP_DENSE_F32 block),
+ * column j at p + j*ld elements, either in HBM (ctx != NULL) or host memory */
 typedef struct {
   msp_ctx *ctx;
-  double *p;
+  void *p;
   int64_t nrows, ld;
   int32_t ncols;
+  int32_t esize;
 } abc_view;
+
+static abc_view dense_view(const msp_dense *D) {
+  const abc_view v = {D->ctx, D->d, D->nrows, D->lda, D->ncols, D->prec == MSP_DENSE_F32 ? 4 : 8};
+  return v;
+}
 
 static int copy_out(const abc_view *v, double *dst) {
   int rc = MSP_SUCCESS;
+  const size_t colb = (size_t)v->nrows * (size_t)v->esize;
   for (int32_t j = 0; j < v->ncols && !rc; ++j) {
-    const double *col = v->p + (size_t)j * v->ld;
-    double *d = dst + (size_t)j * v->nrows;
-    if (v->ctx) rc = mspi_d2h_sync(v->ctx, d, col, (size_t)v->nrows * sizeof(double));
-    else memcpy(d, col, (size_t)v->nrows * sizeof(double));
+    const uint8_t *col = (const uint8_t *)v->p + (size_t)j * (size_t)v->ld * (size_t)v->esize;
+    uint8_t *d = (uint8_t *)dst + (size_t)j * colb;
+    if (v->ctx) rc = mspi_d2h_sync(v->ctx, d, col, colb);
+    else memcpy(d, col, colb);
   }
   return rc;
 }
 
 static int copy_in(const abc_view *v, const double *srcp) {
   int rc = MSP_SUCCESS;
+  const size_t colb = (size_t)v->nrows * (size_t)v->esize;
   for (int32_t j = 0; j < v->ncols && !rc; ++j) {
-    double *col = v->p + (size_t)j * v->ld;
-    const double *s = srcp + (size_t)j * v->nrows;
-    if (v->ctx) rc = mspi_h2d_sync(v->ctx, col, s, (size_t)v->nrows * sizeof(double));
-    else memcpy(col, s, (size_t)v->nrows * sizeof(double));
+    uint8_t *col = (uint8_t *)v->p + (size_t)j * (size_t)v->ld * (size_t)v->esize;
+    const uint8_t *s = (const uint8_t *)srcp + (size_t)j * colb;
+    if (v->ctx) rc = mspi_h2d_sync(v->ctx, col, s, colb);
+    else memcpy(col, s, colb);
   }
   return rc;
 }
@@ -439,10 +450,11 @@ static int publish_device(msp_abcast *b, const abc_view *v, int32_t *published) 
     }
   d->nrows[k] = v->nrows;
   d->ncols[k] = v->ncols;
+  d->esize[k] = v->esize;
   atomic_thread_fence(memory_order_release);
-  const size_t rowb = (size_t)v->nrows * sizeof(double);
-  int rc = mspi_d2d_async2d(b->dctx, b->dbufs + (size_t)k * (size_t)b->cap, rowb, v->p, (size_t)v->ld * sizeof(double),
-                            rowb, (size_t)v->ncols);
+  const size_t rowb = (size_t)v->nrows * (size_t)v->esize;
+  int rc = mspi_d2d_async2d(b->dctx, b->dbufs + (size_t)k * (size_t)b->cap, rowb, v->p,
+                            (size_t)v->ld * (size_t)v->esize, rowb, (size_t)v->ncols);
   if (rc) {
     atomic_store_explicit(&d->claim, P, memory_order_seq_cst);
     return rc;
@@ -476,8 +488,12 @@ static int fetch_device(msp_abcast *b, int32_t src, const abc_view *v, int32_t *
     atomic_store_explicit(mark, 0u, memory_order_seq_cst);
     return berr(MSP_ERR_ARG_SIZ, "received block has a different shape");
   }
-  const size_t rowb = (size_t)v->nrows * sizeof(double);
-  if ((rc = mspi_d2d_async2d(b->dctx, v->p, (size_t)v->ld * sizeof(double), pbuf + (size_t)k * (size_t)b->cap, rowb,
+  if (d->esize[k] != v->esize) { /* nothing copied; the block stays untaken */
+    atomic_store_explicit(mark, 0u, memory_order_seq_cst);
+    return berr(MSP_ERR_ARG_WRONG, "received block was published in another precision than the destination's");
+  }
+  const size_t rowb = (size_t)v->nrows * (size_t)v->esize;
+  if ((rc = mspi_d2d_async2d(b->dctx, v->p, (size_t)v->ld * (size_t)v->esize, pbuf + (size_t)k * (size_t)b->cap, rowb,
                              rowb, (size_t)v->ncols))) {
     atomic_store_explicit(mark, 0u, memory_order_seq_cst);
     return rc;
@@ -506,7 +522,9 @@ static int publish(msp_abcast *b, const abc_view *v, int32_t *published) {
   if (b->dctx && !v->ctx) return berr(MSP_ERR_ARG_WRONG, "device buffers enabled: publish a dense block in HBM");
   if (v->nrows < 0 || v->ncols < 0 || v->ld < v->nrows || (v->nrows > 0 && v->ncols > 0 && !v->p))
     return berr(MSP_ERR_ARG_WRONG, "bad payload shape");
-  if (v->nrows * (int64_t)v->ncols > b->cap) return berr(MSP_ERR_ARG_SIZ, "payload larger than the broadcast slot");
+  /* cap counts doubles: a slot holds twice as many floats */
+  if (v->nrows * (int64_t)v->ncols * v->esize > b->cap * 8)
+    return berr(MSP_ERR_ARG_SIZ, "payload larger than the broadcast slot");
   int rc;
   if (b->dctx) {
     rc = fence_in(b, v);
@@ -528,6 +546,7 @@ static int publish(msp_abcast *b, const abc_view *v, int32_t *published) {
   }
   L->nrows[w] = v->nrows;
   L->ncols[w] = v->ncols;
+  L->esize[w] = v->esize;
   L->version[w] = ++L->published;
   atomic_store_explicit(&L->lock[w], 0u, memory_order_release);
   atomic_store_explicit(&L->newest, w, memory_order_release);
@@ -565,6 +584,10 @@ static int fetch(msp_abcast *b, int32_t src, const abc_view *v, int32_t *got) {
       atomic_fetch_sub_explicit(&L->lock[k], 1u, memory_order_release);
       return berr(MSP_ERR_ARG_SIZ, "received block has a different shape");
     }
+    if (L->esize[k] != v->esize) { /* nothing copied; the block stays untaken */
+      atomic_fetch_sub_explicit(&L->lock[k], 1u, memory_order_release);
+      return berr(MSP_ERR_ARG_WRONG, "received block was published in another precision than the destination's");
+    }
     rc = copy_in(v, buf_at(b, src, k));
     atomic_fetch_sub_explicit(&L->lock[k], 1u, memory_order_release);
     if (rc) return rc;
@@ -578,25 +601,25 @@ static int fetch(msp_abcast *b, int32_t src, const abc_view *v, int32_t *got) {
 int msp_abcast_publish(msp_abcast *b, const double *data, int64_t nrows, int32_t ncols, int64_t ld,
                        int32_t *published) {
   if (!b || !published) return berr(MSP_ERR_ARG_NULL, "NULL argument");
-  const abc_view v = {NULL, (double *)data, nrows, ld, ncols};
+  const abc_view v = {NULL, (void *)data, nrows, ld, ncols, 8};
   return publish(b, &v, published);
 }
 
 int msp_abcast_fetch(msp_abcast *b, int32_t src, double *data, int64_t nrows, int32_t ncols, int64_t ld,
                      int32_t *got) {
   if (!b || !got) return berr(MSP_ERR_ARG_NULL, "NULL argument");
-  const abc_view v = {NULL, data, nrows, ld, ncols};
+  const abc_view v = {NULL, data, nrows, ld, ncols, 8};
   return fetch(b, src, &v, got);
 }
 
 int msp_abcast_publish_dense(msp_abcast *b, const msp_dense *D, int32_t *published) {
   if (!b || !D || !published) return berr(MSP_ERR_ARG_NULL, "NULL argument");
-  const abc_view v = {D->ctx, D->d, D->nrows, D->lda, D->ncols};
+  const abc_view v = dense_view(D);
   return publish(b, &v, published);
 }
 
 int msp_abcast_fetch_dense(msp_abcast *b, int32_t src, msp_dense *D, int32_t *got) {
   if (!b || !D || !got) return berr(MSP_ERR_ARG_NULL, "NULL argument");
-  const abc_view v = {D->ctx, D->d, D->nrows, D->lda, D->ncols};
+  const abc_view v = dense_view(D);
   return fetch(b, src, &v, got);
 }

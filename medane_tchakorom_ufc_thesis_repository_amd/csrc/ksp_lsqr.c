@@ -254,6 +254,9 @@ int msp_lsqr_solve(msp_lsqr *l, msp_vec *const *b, msp_vec *x) {
   const int seq = mspi_reduce_seq(c);
   if (seq && (l->nranks > 1 || l->nloc > MSPI_SEQ_MAXSEG))
     return err(MSP_ERR_SUP, "MSP_REDUCE_SEQ chains the LSQR sums across the row blocks of one process only");
+  for (int k = 0; k < l->nloc && seq; ++k)
+    if (l->R[k]->prec == MSP_DENSE_F32)
+      return err(MSP_ERR_SUP, "MSP_REDUCE_SEQ LSQR over a single-precision R block (MSP_DENSE_F32)");
   double *bd[MSPI_SEQ_MAXSEG];
   for (int k = 0; k < l->nloc && seq; ++k) bd[k] = b[k]->d;
   const int s = l->s, nloc = l->nloc;
@@ -281,14 +284,15 @@ int msp_lsqr_solve(msp_lsqr *l, msp_vec *const *b, msp_vec *x) {
   if ((rc = gather(l, l->gloc, l->gall, 1)) || (rc = mspi_ls_start(c, d))) return rc;
   if (l->o.exact_norm) {
     for (int k = 0; k < nloc; ++k)
-      if ((rc = mspi_dense_colsumsq(c, l->R[k]->d, l->R[k]->lda, s, l->R[k]->nrows, l->partial, l->floc + k * s)))
+      if ((rc = mspi_dense_colsumsq_p(c, l->R[k]->d, l->R[k]->prec, l->R[k]->lda, s, l->R[k]->nrows, l->partial,
+                                      l->floc + k * s)))
         return rc;
     if (seq && (rc = seq_chain(l, NULL, 1, NULL, s, 1, l->floc, s))) return rc;
     if ((rc = gather(l, l->floc, l->fall, s))) return rc;
   }
   for (int k = 0; k < nloc; ++k)
-    if ((rc = mspi_dense_scaled_dots(c, b[k]->d, l->U[k], &d.st->uscale, l->R[k]->d, l->R[k]->lda, s,
-                                     l->R[k]->nrows, l->partial, l->gloc + k * s, stop)))
+    if ((rc = mspi_dense_scaled_dots_p(c, b[k]->d, l->U[k], &d.st->uscale, l->R[k]->d, l->R[k]->prec, l->R[k]->lda, s,
+                                       l->R[k]->nrows, l->partial, l->gloc + k * s, stop)))
       return rc;
   if (seq && (rc = seq_chain(l, NULL, 1, l->U, s, 0, l->gloc, s))) return rc;
   if ((rc = gather(l, l->gloc, l->gall, s)) || (rc = mspi_ls_first(c, d, l->o.exact_norm ? l->fall : NULL)))
@@ -316,8 +320,9 @@ int msp_lsqr_solve(msp_lsqr *l, msp_vec *const *b, msp_vec *x) {
     const double *usc = defer && i > 0 ? &d.st->uscale : NULL;
     if (onepass) { /* one pass over R: U1, ||U1||^2 and R^T U1 (unscaled) per block, one gather, one lane */
       for (int k = 0; k < nloc; ++k)
-        if ((rc = mspi_dense_lsqr_onepass(c, l->R[k]->d, l->R[k]->lda, s, l->R[k]->nrows, d.V, &d.st->nalpha, U[k],
-                                          usc, U1[k], l->partial, l->gloc + k * (s + 1), stop)))
+        if ((rc = mspi_dense_lsqr_onepass_p(c, l->R[k]->d, l->R[k]->prec, l->R[k]->lda, s, l->R[k]->nrows, d.V,
+                                            &d.st->nalpha, U[k], usc, U1[k], l->partial, l->gloc + k * (s + 1),
+                                            stop)))
           return rc;
       if ((rc = gather(l, l->gloc, l->gall, s + 1)) || (rc = mspi_ls_onepass_step(c, d))) return rc;
       if ((i + 1) % LSQR_CHUNK == 0 || i + 1 == nsteps) {
@@ -327,14 +332,14 @@ int msp_lsqr_solve(msp_lsqr *l, msp_vec *const *b, msp_vec *x) {
       continue;
     }
     for (int k = 0; k < nloc; ++k)
-      if ((rc = mspi_dense_gemv(c, l->R[k]->d, l->R[k]->lda, s, l->R[k]->nrows, d.V, &d.st->nalpha, U[k], usc,
-                                U1[k], l->partial, l->gloc + k, stop)))
+      if ((rc = mspi_dense_gemv_p(c, l->R[k]->d, l->R[k]->prec, l->R[k]->lda, s, l->R[k]->nrows, d.V, &d.st->nalpha,
+                                  U[k], usc, U1[k], l->partial, l->gloc + k, stop)))
         return rc;
     if (seq && (rc = seq_chain(l, U1, 0, NULL, 1, 0, l->gloc, 1))) return rc;
     if ((rc = gather(l, l->gloc, l->gall, 1)) || (rc = mspi_ls_beta(c, d))) return rc;
     for (int k = 0; k < nloc; ++k)
-      if ((rc = mspi_dense_scaled_dots(c, U1[k], defer ? NULL : U1[k], &d.st->uscale, l->R[k]->d, l->R[k]->lda, s,
-                                       l->R[k]->nrows, l->partial, l->gloc + k * s, stop)))
+      if ((rc = mspi_dense_scaled_dots_p(c, U1[k], defer ? NULL : U1[k], &d.st->uscale, l->R[k]->d, l->R[k]->prec,
+                                         l->R[k]->lda, s, l->R[k]->nrows, l->partial, l->gloc + k * s, stop)))
         return rc;
     if (seq && (rc = seq_chain(l, NULL, 1, U1, s, 0, l->gloc, s))) return rc;
     if ((rc = gather(l, l->gloc, l->gall, s)) || (rc = mspi_ls_step(c, d))) return rc;

@@ -57,15 +57,18 @@ typedef struct {
 mspi_csr_view mspi_mat_csr(const msp_mat *A);
 /* R = A S over DV storage (ELL layout); MSP_ERR_SUP when A is not in it */
 int mspi_mat_spmm_dv(msp_mat *A, const double *S, int64_t lds, int nc, int64_t srows, double *R, int64_t ldr);
+/* the same into a float R (each f64 row sum rounded once); always the ELL SpMM */
+int mspi_mat_spmm_dv_f32(msp_mat *A, const double *S, int64_t lds, int nc, int64_t srows, float *R, int64_t ldr);
 
-/* dense row block, column-major, lda a multiple of 512 */
+/* dense row block, column-major, lda (in elements) a multiple of 512 (doubles) or 1024 (floats) */
 struct msp_dense {
   msp_ctx *ctx;
   int64_t nrows;
   int32_t ncols;
   int64_t lda;
-  double *d;
+  double *d; /* the storage; floats when prec == MSP_DENSE_F32 */
   int view; /* msp_dense_create_view: columns of another block, storage not freed */
+  int prec; /* MSP_DENSE_F64 / MSP_DENSE_F32 */
 };
 
 /* y = A[:, 0:nc] coef (+ (*nal_dev) U when U != NULL, skipped when *nal_dev == 0); usc_dev != NULL: U is
@@ -87,6 +90,21 @@ int mspi_dense_lsqr_onepass(msp_ctx *ctx, const double *A, int64_t lda, int nc, 
 /* out_dev[j] = ||column j||^2 (DBR) */
 int mspi_dense_colsumsq(msp_ctx *ctx, const double *A, int64_t lda, int nc, int64_t n, double *partial,
                         double *out_dev);
+
+/* The four above over a block of either precision: A points at its elements, prec is MSP_DENSE_F64 or
+ * MSP_DENSE_F32 (floats promoted as read; every sum f64, in the same order).  MSP_REDUCE_SEQ with an F32 block:
+ * MSP_ERR_SUP. */
+int mspi_dense_gemv_p(msp_ctx *ctx, const void *A, int prec, int64_t lda, int nc, int64_t n, const double *coef_dev,
+                      const double *nal_dev, const double *U, const double *usc_dev, double *y, double *partial,
+                      double *sumsq_dev, const int *stop);
+int mspi_dense_scaled_dots_p(msp_ctx *ctx, const double *win, double *wout, const double *sc_dev, const void *A,
+                             int prec, int64_t lda, int nc, int64_t n, double *partial, double *out_dev,
+                             const int *stop);
+int mspi_dense_lsqr_onepass_p(msp_ctx *ctx, const void *A, int prec, int64_t lda, int nc, int64_t n,
+                              const double *coef_dev, const double *nal_dev, const double *U, const double *usc_dev,
+                              double *y, double *partial, double *out_dev, const int *stop);
+int mspi_dense_colsumsq_p(msp_ctx *ctx, const void *A, int prec, int64_t lda, int nc, int64_t n, double *partial,
+                          double *out_dev);
 
 /* y = A x ; r = b - A x */
 int mspi_spmv(msp_mat *A, const double *x, double *y);

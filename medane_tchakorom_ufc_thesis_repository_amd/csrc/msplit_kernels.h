@@ -167,6 +167,9 @@ int msk_box_maxpy_march(int32_t nx, int64_t P, int64_t n, int d2, const uint8_t*
 // R[:, 0:nc] = A S[:, 0:nc] over DV storage in the ELL layout (W codes per row)
 int msk_spmm_ell(int32_t nrows, int W, const uint8_t* code8, const int32_t* ddelta, const double* dval, int ndict,
                  const double* S, int64_t lds, int nc, double* R, int64_t ldr, hipStream_t s);
+// the same with R stored as float: each f64 row sum rounded once at the store (MSP_DENSE_F32)
+int msk_spmm_ell_f32(int32_t nrows, int W, const uint8_t* code8, const int32_t* ddelta, const double* dval, int ndict,
+                     const double* S, int64_t lds, int nc, float* R, int64_t ldr, hipStream_t s);
 int msk_ell_encode(int32_t nrows, int W, const int32_t* rowptr, const int32_t* col, const double* val, int ndict,
                    const int32_t* ddelta, const double* dval, uint8_t* code8, int* fail, hipStream_t s);
 // DV codes of an assembled CSR against a dictionary; *fail (device) set when it does not fit
@@ -181,6 +184,8 @@ int msk_spmv_mdot(int32_t nrows, const int32_t* rowptr, const int32_t* col, cons
 // R[:, 0:nc] = A S[:, 0:nc], column-major S (lds) and R (ldr); needs lds_cap > 0
 int msk_spmm(int32_t nrows, const int32_t* rowptr, const int32_t* col, const double* val, const double* S,
              int64_t lds, int nc, double* R, int64_t ldr, int32_t lds_cap, hipStream_t s);
+int msk_spmm_f32(int32_t nrows, const int32_t* rowptr, const int32_t* col, const double* val, const double* S,
+                 int64_t lds, int nc, float* R, int64_t ldr, int32_t lds_cap, hipStream_t s);
 int msk_spmv_rows(int32_t nlisted, const int32_t* row_ids, const int32_t* rowptr, const int32_t* col,
                   const double* val, const double* x, const double* b, double* y, int resid, hipStream_t s);
 // lo/hi: extra coupling columns to the neighbour plane below/above (column space [lo | block | hi])

@@ -823,11 +823,13 @@ __global__ __launch_bounds__(kT) void k_spmv_mdot(int32_t nrows, const int32_t* 
 
 // R[:, 0:nc] = A S[:, 0:nc] (MatMatMult(AIJ, DENSE)): the row block's CSR slice
 // is staged once, then each column streams through it like one SpMV (per row:
-// entries in order, from 0), so A is read once for all nc columns.
+// entries in order, from 0), so A is read once for all nc columns.  TR: R's element type; a float R takes
+// the f64 row sum rounded once at the store (MSP_DENSE_F32).
+template <typename TR>
 __global__ __launch_bounds__(kT) void k_spmm_lds8(int32_t nrows, const int32_t* __restrict__ rowptr,
                                                   const int32_t* __restrict__ col, const double* __restrict__ val,
                                                   const double* __restrict__ S, int64_t lds, int nc,
-                                                  double* __restrict__ R, int64_t ldr, int32_t lds_cap) {
+                                                  TR* __restrict__ R, int64_t ldr, int32_t lds_cap) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   double* sval = reinterpret_cast<double*>(smem);
   int32_t* scol = reinterpret_cast<int32_t*>(smem + (size_t)lds_cap * 8);
@@ -863,7 +865,7 @@ __global__ __launch_bounds__(kT) void k_spmm_lds8(int32_t nrows, const int32_t* 
       for (int u = 0; u < 8; ++u)
         if (kb + u < k1) s = s + av[u] * xv[u];
     }
-    R[r + (int64_t)q * ldr] = s;
+    R[r + (int64_t)q * ldr] = (TR)s;
   }
 }
 
@@ -2653,11 +2655,11 @@ __global__ __launch_bounds__(kT) void k_march_check(int32_t nrows, int32_t nx, i
 // MatMatMult R = A S over DV storage (ELL layout): lane per row, its codes
 // decoded once into (delta, value) registers, then every column of S streamed
 // past them; each R(r, q) is the CSR row sum of k_spmm_lds8 term for term.
-template <int W>
+template <int W, typename TR>
 __global__ __launch_bounds__(kT) void k_spmm_ell(int32_t nrows, const uint8_t* __restrict__ code8,
                                                  const int32_t* __restrict__ ddelta, const double* __restrict__ dval,
                                                  int ndict, const double* __restrict__ S, int64_t lds, int nc,
-                                                 double* __restrict__ R, int64_t ldr) {
+                                                 TR* __restrict__ R, int64_t ldr) {
   typedef EllWord<W> EW;
   typedef typename EW::T CT;
   __shared__ int32_t sdel[256];
@@ -2691,7 +2693,7 @@ __global__ __launch_bounds__(kT) void k_spmm_ell(int32_t nrows, const uint8_t* _
 #pragma unroll
     for (int q = 0; q < W; ++q)
       if (ok[q]) s = s + av[q] * xv[q];
-    R[r + (int64_t)j * ldr] = s;
+    R[r + (int64_t)j * ldr] = (TR)s;  // float R: the f64 row sum rounded once
   }
 }
 
@@ -3333,15 +3335,27 @@ extern "C" int msk_spmv_dv(int32_t nrows, const int32_t* rowptr, const uint8_t* 
   return (int)hipGetLastError();
 }
 
-extern "C" int msk_spmm_ell(int32_t nrows, int W, const uint8_t* code8, const int32_t* ddelta, const double* dval,
-                            int ndict, const double* S, int64_t lds, int nc, double* R, int64_t ldr, hipStream_t s) {
+template <typename TR>
+static int spmm_ell_launch(int32_t nrows, int W, const uint8_t* code8, const int32_t* ddelta, const double* dval,
+                           int ndict, const double* S, int64_t lds, int nc, TR* R, int64_t ldr, hipStream_t s) {
   if (nrows <= 0 || nc <= 0) return 0;
   const unsigned g = (unsigned)((nrows + kT - 1) / kT);
-  if (W == 4) k_spmm_ell<4><<<g, kT, 0, s>>>(nrows, code8, ddelta, dval, ndict, S, lds, nc, R, ldr);
-  else if (W == 8) k_spmm_ell<8><<<g, kT, 0, s>>>(nrows, code8, ddelta, dval, ndict, S, lds, nc, R, ldr);
-  else if (W == 16) k_spmm_ell<16><<<g, kT, 0, s>>>(nrows, code8, ddelta, dval, ndict, S, lds, nc, R, ldr);
+  if (W == 4) k_spmm_ell<4, TR><<<g, kT, 0, s>>>(nrows, code8, ddelta, dval, ndict, S, lds, nc, R, ldr);
+  else if (W == 8) k_spmm_ell<8, TR><<<g, kT, 0, s>>>(nrows, code8, ddelta, dval, ndict, S, lds, nc, R, ldr);
+  else if (W == 16) k_spmm_ell<16, TR><<<g, kT, 0, s>>>(nrows, code8, ddelta, dval, ndict, S, lds, nc, R, ldr);
   else return (int)hipErrorInvalidValue;
   return (int)hipGetLastError();
+}
+
+extern "C" int msk_spmm_ell(int32_t nrows, int W, const uint8_t* code8, const int32_t* ddelta, const double* dval,
+                            int ndict, const double* S, int64_t lds, int nc, double* R, int64_t ldr, hipStream_t s) {
+  return spmm_ell_launch<double>(nrows, W, code8, ddelta, dval, ndict, S, lds, nc, R, ldr, s);
+}
+
+extern "C" int msk_spmm_ell_f32(int32_t nrows, int W, const uint8_t* code8, const int32_t* ddelta,
+                                const double* dval, int ndict, const double* S, int64_t lds, int nc, float* R,
+                                int64_t ldr, hipStream_t s) {
+  return spmm_ell_launch<float>(nrows, W, code8, ddelta, dval, ndict, S, lds, nc, R, ldr, s);
 }
 
 extern "C" int msk_ell_encode(int32_t nrows, int W, const int32_t* rowptr, const int32_t* col, const double* val,
@@ -3565,7 +3579,19 @@ extern "C" int msk_spmm(int32_t nrows, const int32_t* rowptr, const int32_t* col
   if (nrows <= 0 || nc <= 0) return 0;
   if (lds_cap <= 0) return (int)hipErrorInvalidValue;  // rows too long for the LDS stage
   const unsigned g = (unsigned)((nrows + kT - 1) / kT);
-  k_spmm_lds8<<<dim3(g), dim3(kT), (size_t)lds_cap * 12, s>>>(nrows, rowptr, col, val, S, lds, nc, R, ldr, lds_cap);
+  k_spmm_lds8<double><<<dim3(g), dim3(kT), (size_t)lds_cap * 12, s>>>(nrows, rowptr, col, val, S, lds, nc, R, ldr,
+                                                                      lds_cap);
+  return (int)hipGetLastError();
+}
+
+extern "C" int msk_spmm_f32(int32_t nrows, const int32_t* rowptr, const int32_t* col, const double* val,
+                            const double* S, int64_t lds, int nc, float* R, int64_t ldr, int32_t lds_cap,
+                            hipStream_t s) {
+  if (nrows <= 0 || nc <= 0) return 0;
+  if (lds_cap <= 0) return (int)hipErrorInvalidValue;
+  const unsigned g = (unsigned)((nrows + kT - 1) / kT);
+  k_spmm_lds8<float><<<dim3(g), dim3(kT), (size_t)lds_cap * 12, s>>>(nrows, rowptr, col, val, S, lds, nc, R, ldr,
+                                                                     lds_cap);
   return (int)hipGetLastError();
 }
 

@@ -1383,6 +1383,16 @@ extern "C" void mspi_graph_destroy(void* exec) {
   if (exec) (void)hipGraphExecDestroy((hipGraphExec_t)exec);
 }
 
+extern "C" int mspi_mat_spmm_dv_f32(msp_mat* A, const double* S, int64_t lds, int nc, int64_t srows, float* R,
+                                    int64_t ldr) {
+  if (!A->dv_on || !A->dv_w) return MSP_ERR_SUP;
+  // a float R always takes the ELL SpMM (the box march is an SpMV that stores doubles); the row sums are the same
+  KTimer kt(A->ctx, MSP_KERNEL_SPMM, (double)A->dv_w * A->nrows + (double)nc * (8.0 * srows + 4.0 * A->nrows));
+  KCHK(msk_spmm_ell_f32(A->nrows, A->dv_w, A->dv_code, A->dv_delta, A->dv_val, A->ndict, S, lds, nc, R, ldr,
+                        A->ctx->stream));
+  return MSP_SUCCESS;
+}
+
 extern "C" int mspi_mat_spmm_dv(msp_mat* A, const double* S, int64_t lds, int nc, int64_t srows, double* R,
                                 int64_t ldr) {
   if (!A->dv_on || !A->dv_w) return MSP_ERR_SUP;

@@ -22,7 +22,7 @@ import os
 import time
 from dataclasses import dataclass, field
 
-from .petsc import Context, DenseMat, Mat, Options, Vec
+from .petsc import PETSC_ERR_ARG_OUTOFRANGE, Context, DenseMat, Mat, MsplitError, Options, Vec
 from .utils import BlockLayout, block_layout, initializeKSP, initializeOuterKSP, inner_solver, updateLocalRHS
 
 
@@ -125,15 +125,30 @@ class GpuBlock:
         return ln * ln
 
     # -- global minimization (SMSM-global) hooks
-    def setup_minimization(self, s: int):
+    def minimization_precision(self, precision: str | None = None, opts: Options | None = None) -> str:
+        """Storage precision of R = A S: the explicit argument, else -msplit_minimization_precision
+        double|single (unprefixed, like -msplit_minimization), else double.  "single" stores R as float
+        (DenseMat precision); S, the Gram parts and every sum stay double."""
+        if precision is None:
+            o = opts if opts is not None else self.opts
+            precision = o.get_string("msplit_minimization_precision", "double") if o is not None else "double"
+        word = str(precision).lower()
+        if word not in DenseMat.PRECISIONS:
+            raise MsplitError(PETSC_ERR_ARG_OUTOFRANGE, f"-msplit_minimization_precision {precision}: expected one "
+                              f"of {tuple(DenseMat.PRECISIONS)}")
+        return word
+
+    def setup_minimization(self, s: int, precision: str | None = None):
         """S (the s latest iterates, with the neighbour planes R = A S reads) and
         R = A S in HBM, and A_ext = this block's rows of A_block_jacobi with the
-        coupling columns (create_redistributed_A_block_jacobi, utils.c:891-921)."""
+        coupling columns (create_redistributed_A_block_jacobi, utils.c:891-921).
+        precision: minimization_precision."""
         L = self.layout
         self.s = int(s)
+        self.r_precision = self.minimization_precision(precision)
         self._ensure_ext()
         self.S = DenseMat(self.ctx, self.lo_rows + L.nrows + self.hi_rows, self.s)
-        self.R = DenseMat(self.ctx, L.nrows, self.s)
+        self.R = DenseMat(self.ctx, L.nrows, self.s, self.r_precision)
 
     def _ensure_ext(self):
         """A_ext: the block's full rows of A_block_jacobi, coupling columns kept."""
@@ -152,14 +167,16 @@ class GpuBlock:
             M.release_csr()
 
     # -- local minimization (SMSM-local, AMAM-local) hooks
-    def setup_local_minimization(self, s: int, opts: Options | None, prefix: str | None = None):
+    def setup_local_minimization(self, s: int, opts: Options | None, prefix: str | None = None,
+                                 precision: str | None = None):
         """S_i (the block's own s latest iterates), R_i = A_ii S_i and a one-block
         LSQR (create_matrix_dense of N/nb x s, SMSM-local.c / AMAM-local_prime.c:246-253;
-        outer KSP prefix outer{b+1}_)."""
+        outer KSP prefix outer{b+1}_).  precision: minimization_precision (of R_i)."""
         self.s = int(s)
         n = self.layout.nrows
+        self.r_precision = self.minimization_precision(precision, opts)
         self.S_loc = DenseMat(self.ctx, n, self.s)
-        self.R_loc = DenseMat(self.ctx, n, self.s)
+        self.R_loc = DenseMat(self.ctx, n, self.s, self.r_precision)
         self.alpha_loc = Vec(self.ctx, self.s)
         self.lsqr_loc = initializeOuterKSP(self.ctx, prefix if prefix is not None else f"outer{self.layout.b + 1}_",
                                            opts)
@@ -204,7 +221,7 @@ class GpuBlock:
     MINIMIZATIONS = ("lsqr", "rtr")
 
     def setup_global_async_minimization(self, s: int, opts: Options | None = None, prefix: str | None = None,
-                                        minimization: str | None = None):
+                                        minimization: str | None = None, precision: str | None = None):
         """AMAM-global_prime.c:238-330: S over the block's rows and neighbour planes,
         this block's rows of R, the replicated R -- every block's rows, zero until
         that block's first message arrives (MatZeroEntries(R)) --, the global b and
@@ -216,9 +233,12 @@ class GpuBlock:
         publishes those s(s+1) doubles newest-value; every block sums the newest parts in
         block order (zeros before a block's first message: R_j = 0 gives G_j = 0) and runs
         the outer KSP (lsqr, the same options) on G alpha = c.  No replicated R or b: a
-        block holds its own rows only, whatever the block count."""
+        block holds its own rows only, whatever the block count.
+
+        precision: minimization_precision, of R and of every block's rows of the replicated R (half the HBM
+        and half the bytes of each broadcast); Gc and Gsum stay double."""
         L = self.layout
-        self.setup_minimization(s)
+        self.setup_minimization(s, self.minimization_precision(precision, opts))
         if minimization is None:
             o = opts if opts is not None else self.opts
             minimization = o.get_string("msplit_minimization", "lsqr").lower() if o is not None else "lsqr"
@@ -250,7 +270,7 @@ class GpuBlock:
                 self.b_all.append(self.b)
                 continue
             Lj = block_layout(L.dim, L.nx, L.ny, L.nz, L.nb, j, L.peclet)
-            R = DenseMat(self.ctx, Lj.nrows, self.s)
+            R = DenseMat(self.ctx, Lj.nrows, self.s, self.r_precision)
             R.zero_entries()
             self.R_rep.append(R)
             lo = any(nbr < j for nbr, *_ in Lj.recv)
@@ -267,10 +287,11 @@ class GpuBlock:
         self.alpha_glob = Vec(self.ctx, self.s)
 
     def bcast_cap(self) -> int:
-        """Doubles one block publishes per minimization: its rows of R, or its Gram part."""
+        """Doubles one block publishes per minimization: its rows of R (half as many when R is stored single),
+        or its Gram part."""
         if getattr(self, "minimization", "lsqr") == "rtr":
             return self.s * (self.s + 1)
-        return self.R.shape[0] * self.R.shape[1]
+        return slot_doubles(self.R)
 
     def global_async_minimize(self, bcast):
         """AMAM-global_prime.c:415-440: R_i = A_block S, send it (comm_async_test_and_send_min),
@@ -364,6 +385,13 @@ class GpuBlock:
         d.waxpy(-1.0, ones, self.x)
         e = d.norm()
         return e * e
+
+
+def slot_doubles(R) -> int:
+    """The doubles a broadcast slot needs for R's entries: two floats of a single-precision DenseMat fill one
+    (a host block of the CPU twin runs holds numpy doubles)."""
+    n = R.shape[0] * R.shape[1]
+    return (n + 1) // 2 if isinstance(R, DenseMat) and R.get_precision() == "single" else n
 
 
 @dataclass

@@ -391,12 +391,27 @@ class Mat:
 # ----------------------------------------------------------------------- dense
 class DenseMat:
     """Rows of a MATDENSE matrix in HBM, column-major (create_matrix_dense,
-    utils.c:123-137, + MatZeroEntries)."""
+    utils.c:123-137, + MatZeroEntries).  precision "single" (msp_dense_create_prec, MSP_DENSE_F32) stores
+    the entries as float -- each rounded once when it is stored, promoted as it is read; every sum stays f64 --:
+    the compressed R = A S of the minimization (-msplit_minimization_precision)."""
 
-    def __init__(self, ctx: Context, nrows: int, ncols: int):
+    PRECISIONS = {"double": 0, "single": 1}               # MSP_DENSE_F64, MSP_DENSE_F32
+
+    @classmethod
+    def precision_code(cls, precision) -> int:
+        word = str(precision).lower()
+        if word not in cls.PRECISIONS:
+            raise MsplitError(PETSC_ERR_ARG_OUTOFRANGE,
+                              f"dense precision {precision!r}: expected one of {tuple(cls.PRECISIONS)}")
+        return cls.PRECISIONS[word]
+
+    def __init__(self, ctx: Context, nrows: int, ncols: int, precision: str = "double"):
         self.ctx = ctx
         h = C.c_void_p()
-        call("msp_dense_create", ctx.h, int(nrows), int(ncols), C.byref(h))
+        if precision == "double":
+            call("msp_dense_create", ctx.h, int(nrows), int(ncols), C.byref(h))
+        else:
+            call("msp_dense_create_prec", ctx.h, int(nrows), int(ncols), self.precision_code(precision), C.byref(h))
         self.h = h
         self.shape = (int(nrows), int(ncols))
         lda = C.c_int64()
@@ -404,11 +419,16 @@ class DenseMat:
         self.lda = lda.value
 
     @classmethod
-    def from_array(cls, ctx: Context, a) -> "DenseMat":
+    def from_array(cls, ctx: Context, a, precision: str = "double") -> "DenseMat":
         a = np.asfortranarray(a, np.float64)
-        M = cls(ctx, a.shape[0], a.shape[1])
+        M = cls(ctx, a.shape[0], a.shape[1], precision)
         M.set_values(a)
         return M
+
+    def get_precision(self) -> str:
+        v = C.c_int()
+        call("msp_dense_get_precision", self.h, C.byref(v))
+        return {c: w for w, c in self.PRECISIONS.items()}[v.value]
 
     def set_values(self, a):
         a = np.asfortranarray(a, np.float64)
@@ -459,6 +479,12 @@ class DenseMat:
     def device_ptr(self) -> int:
         p = C.c_void_p()
         call("msp_dense_get_array", self.h, C.byref(p))
+        return p.value
+
+    def device_ptr_f32(self) -> int:
+        """The float storage of a "single" block (msp_dense_get_array_f32)."""
+        p = C.c_void_p()
+        call("msp_dense_get_array_f32", self.h, C.byref(p))
         return p.value
 
     @staticmethod

@@ -24,6 +24,11 @@ static const char *const MSplitReductions[] = {"dbr", "seq", "MSplitReduction", 
  * (include/msplit.h msp_ksp_set_basis_precision); single excludes -msplit_reduction seq */
 static const char *const MSplitBasisPrecisions[] = {"double", "single", "MSplitBasisPrecision", "MSPLIT_BASIS_", NULL};
 
+/* -msplit_minimization_precision: the operator R of msplitlsqr stored in HBM as double, or as float with all
+ * arithmetic in double (include/msplit.h msp_dense_create_prec); single excludes -msplit_reduction seq */
+static const char *const MSplitMinimizationPrecisions[] = {"double", "single", "MSplitMinimizationPrecision",
+                                                           "MSPLIT_MINIMIZATION_", NULL};
+
 #define MSPCall(e) do { int _rc = (e); PetscCheck(!_rc, PETSC_COMM_SELF, _rc, "%s", msp_get_last_error()); } while (0)
 
 /* -msplit_reduction under a KSP's prefix: that order for this KSP's solves only.  The process's one context also
@@ -317,6 +322,7 @@ typedef struct {
   msp_vec *b, *x;
   PetscBool exact_norm;
   PetscInt reduction; /* -msplit_reduction, as for msplitgmres (-1: the shared context's order) */
+  PetscInt r_precision; /* -msplit_minimization_precision double|single: MSP_DENSE_F64 / MSP_DENSE_F32 */
 } KSP_MSplitLSQR;
 
 static PetscErrorCode KSPSetUp_MSplitLSQR(KSP ksp)
@@ -336,7 +342,8 @@ static PetscErrorCode KSPSetUp_MSplitLSQR(KSP ksp)
   PetscCall(MatDenseGetLDA(Al, &lda));
   if (!ms->ctx) PetscCall(MSplitContext(&ms->ctx));
   MSPCall(msp_dense_destroy(&ms->R));
-  MSPCall(msp_dense_create(ms->ctx, m, (int32_t)n, &ms->R));
+  /* MSP_DENSE_F32: set_values below rounds on the device */
+  MSPCall(msp_dense_create_prec(ms->ctx, m, (int32_t)n, (int)ms->r_precision, &ms->R));
   PetscCall(MatDenseGetArrayRead(Al, &a));
   MSPCall(msp_dense_set_values(ms->R, a, lda));
   PetscCall(MatDenseRestoreArrayRead(Al, &a));
@@ -404,6 +411,10 @@ static PetscErrorCode KSPSetFromOptions_MSplitLSQR(KSP ksp, PetscOptionItems *Pe
   PetscCall(MSplitSetFromOptionsReduction(PetscOptionsObject, &ms->reduction));
   PetscCall(PetscOptionsBool("-ksp_lsqr_exact_mat_norm", "exact Frobenius norm of the operator", NULL,
                              ms->exact_norm, &ms->exact_norm, NULL));
+  PetscEnum rp = (PetscEnum)ms->r_precision;
+  PetscCall(PetscOptionsEnum("-msplit_minimization_precision", "storage precision of the operator R = A S", NULL,
+                             MSplitMinimizationPrecisions, rp, &rp, NULL));
+  ms->r_precision = (PetscInt)rp;
   PetscOptionsHeadEnd();
   PetscFunctionReturn(PETSC_SUCCESS);
 }
