@@ -4,7 +4,7 @@
 // The basis is the step's traffic, so storing it in four bytes per entry instead of eight is what
 // moves an HBM-bound step.  Only the storage changes: every value is promoted to double as it is loaded and all
 // arithmetic is the f64 path's, statement for statement (-ffp-contract=off, the DBR reduction order of
-// msplit_kernels.hip, PETSc's VecMAXPY grouping).  A vector is rounded once, when it is stored:
+// msplit_kdev.hpp, PETSc's VecMAXPY grouping).  A vector is rounded once, when it is stored:
 //   rnd(v) = (double)(float)v   -- round to nearest even, gradual underflow, overflow to +-inf
 // (v_cvt_f32_f64 under the kernel's default mode: f32 denormals are kept on gfx950 code objects), and its norm is
 // taken of the rounded values -- what is in memory is the vector.

@@ -32,7 +32,7 @@ __device__ __forceinline__ bool stopped(const int* stop) { return stop && *stop;
 
 // Column loads: VEC 0 = scalar (unaligned / ragged), 1 = 16-byte default policy,
 // 2 = 16-byte non-temporal (the default: the columns of S and R stream through
-// once per launch and dwarf the MALL; msplit_kernels.hip, MSK_TUNE_VEC_TEMPORAL).
+// once per launch and dwarf the MALL; msplit_kdev.hpp dot_chunk, MSK_TUNE_VEC_TEMPORAL).
 typedef double dx2 __attribute__((ext_vector_type(2)));
 template <int VEC>
 __device__ __forceinline__ double2 ld_col(const double* p) {

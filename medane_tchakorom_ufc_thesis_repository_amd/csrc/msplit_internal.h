@@ -1,6 +1,6 @@
 /*
  * msplit_internal.h -- what the C host side (ksp_gmres.c) needs from the HIP
- * side (msplit_runtime.hip / msplit_kernels.hip).  Raw device pointers, all
+ * side (msplit_runtime.hip / msplit_kernels.hip / msplit_k_*.hip).  Raw device pointers, all
  * work stream-ordered on the context's stream.
  */
 #ifndef MSPLIT_INTERNAL_H

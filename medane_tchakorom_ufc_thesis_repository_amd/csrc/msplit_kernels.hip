@@ -17,528 +17,13 @@
 #include <cstdint>
 
 #include "msplit_kernels.h"
+#include "msplit_kdev.hpp"
 
-// The launchers are split into parts that the Makefile compiles as separate objects (-DMSK_PART=1..6), so the
-// large template sets (MDot and MAXPY over 1..32 vectors and their variants) build in parallel.  Without
-// MSK_PART the file compiles every part into one object.
-#ifndef MSK_PART
-#define MSK_PART 0
-#endif
-#define MSK_IN(p) (MSK_PART == 0 || MSK_PART == (p))
-#define MSK_PART_DOT 1
-#define MSK_PART_MAXPY 2
-#define MSK_PART_SPMV 3
-#define MSK_PART_MISC 4
-#define MSK_PART_DOT_A 5
-#define MSK_PART_DOT_B 6
+// The DBR dots and the MAXPY are msplit_k_dot*.hip and msplit_k_maxpy.hip; what they share with this file is
+// msplit_kdev.hpp.
 
 namespace msk {
-namespace {  // internal linkage: this file is compiled once per part (see MSK_PART below)
-
-constexpr int kT = 256;                  // threads per workgroup (4 wave64)
-constexpr int kIters = 8;                // double2 slices per thread per DBR chunk
-constexpr int kChunk = kT * 2 * kIters;  // 4096 elements per DBR chunk
-
-static_assert(kChunk == MSK_DBR_CHUNK, "DBR chunk must match the oracle");
-
-__device__ __forceinline__ bool stopped(const int* stop) { return stop && *stop; }
-
-typedef double dx2 __attribute__((ext_vector_type(2)));
-typedef int ix4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ double2 ld_nt(const double2* p) {
-  const dx2 v = __builtin_nontemporal_load(reinterpret_cast<const dx2*>(p));
-  return make_double2(v.x, v.y);
-}
-__device__ __forceinline__ int4 ld_nt(const int4* p) {
-  const ix4 v = __builtin_nontemporal_load(reinterpret_cast<const ix4*>(p));
-  return make_int4(v.x, v.y, v.z, v.w);
-}
-
-__device__ __forceinline__ const double* vec_at(const Vecs& V, int j) {
-  return V.base ? V.base + (int64_t)j * V.stride : V.p[j];
-}
-// deferred VecNormalize: element i of vector j is fl(V_j[i] * scale[j]); x * 1.0
-// is exact for every double, so unscaled sets multiply by 1.0 (wave-uniform load)
-__device__ __forceinline__ double vec_scale(const Vecs& V, int j) { return V.scale ? V.scale[j] : 1.0; }
-
-// ---------------------------------------------- W = A (sc x) in the CGS kernels
-typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
-
-// Stage the DV dictionary in LDS (the caller synchronises before use).
-__device__ __forceinline__ void ell_dict_stage(const EllOp& op, int32_t* sdel, double* sval) {
-  const int t = threadIdx.x;
-  if (t < op.ndict) {
-    sdel[t] = op.ddelta[t];
-    sval[t] = op.dval[t];
-  } else {
-    sdel[t] = 0;  // code 255 (no entry) and unused codes: delta 0, never added
-    sval[t] = 0.0;
-  }
-}
-
-// The lane's W values at its DBR positions base + j*512 + {0,1}, j in [J0, J0+JN):
-// rows e, e+1 read their 2 x 8 codes with one 16-byte load, then every gather
-// of the pair is issued before the first product (padding entries gather x[0]
-// and are masked out).  Each row sums val * (x * sc) over its entries in CSR
-// order from 0.0 -- k_spmv_ell's SCALED sum, term for term.  Rows >= n: 0.
-template <int J0, int JN>
-__device__ __forceinline__ void ell_rows(const EllOp& op, const int32_t* sdel, const double* sval, double sc,
-                                         int64_t base, int64_t n, double (&wr)[2 * kIters]) {
-#pragma unroll
-  for (int j = J0; j < J0 + JN; ++j) {
-    const int64_t e = base + j * (2 * kT);
-    u32x4v cw = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
-    if (e + 1 < n) {
-      cw = __builtin_nontemporal_load(reinterpret_cast<const u32x4v*>(op.code8 + e * 8));
-    } else if (e < n) {
-      cw.x = reinterpret_cast<const uint32_t*>(op.code8 + e * 8)[0];
-      cw.y = reinterpret_cast<const uint32_t*>(op.code8 + e * 8)[1];
-    }
-    int32_t ix[16];
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const uint32_t w4 = q < 4 ? cw.x : q < 8 ? cw.y : q < 12 ? cw.z : cw.w;
-      const int c = (w4 >> (8 * (q & 3))) & 255;
-      ix[q] = c != 255 ? (int32_t)(e + (q >> 3)) + sdel[c] : 0;
-    }
-    double xv[16];
-#pragma unroll
-    for (int q = 0; q < 16; ++q) xv[q] = op.x[ix[q]];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      double acc = 0.0;
-#pragma unroll
-      for (int q = 8 * h; q < 8 * h + 8; ++q) {
-        const uint32_t w4 = q < 4 ? cw.x : q < 8 ? cw.y : q < 12 ? cw.z : cw.w;
-        const int c = (w4 >> (8 * (q & 3))) & 255;
-        const double sn = acc + sval[c] * (xv[q] * sc);
-        acc = c != 255 ? sn : acc;
-      }
-      wr[2 * j + h] = acc;
-    }
-  }
-}
-
-__device__ __forceinline__ double wave_butterfly(double v) {
-  // v[l] <- v[l] + v[l ^ off], off = 32..1: every lane ends with the same sum.
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_xor(v, off, 64);
-  return v;
-}
-
-// ---------------------------------------------------------------- DBR dots
-// Stage 1: workgroup c reduces chunk c of every vector: lane t accumulates its
-// elements base + j*512 + 2t, +1 (j = 0..7) in order, wave butterfly, then
-// (w0 + w1) + (w2 + w3).  partial[v * nchunks + c].  w stays in registers and
-// each vector streams 32 KiB contiguous per workgroup.
-// VAR: bit 0 = non-temporal loads of the basis vectors (the default: each
-// vector streams through once per kernel and is far larger than the 256 MiB
-// MALL, so caching it only evicts lines others still need; +8-16 % per kernel,
-// +7.7 % per GMRES step on 256^3, same-box A/B); bit 2 = non-temporal store
-// of w in MAXPY.  Results are identical.
-// G vectors of a full chunk at once: all G*8 loads are issued before the first
-// product (4 x 32 KiB in flight per workgroup instead of one vector's 32 KiB),
-// then G independent accumulations and butterflies.  Per vector the sum is the
-// same sequence as one at a time.
-template <int G, int VAR>
-__device__ __forceinline__ void dot_group_full(const double (&wr)[2 * kIters], const Vecs& V, int64_t base, int rev,
-                                               int nv, int g, double (*red)[4], int lane, int wv) {
-  double2 q[G][kIters];
-  double sv[G];
-  int vv[G];
-#pragma unroll
-  for (int u = 0; u < G; ++u) {
-    // load order only (each dot is independent): newest vector first when rev
-    vv[u] = rev ? nv - 1 - (g + u) : g + u;
-    const double* __restrict__ y = vec_at(V, vv[u]);
-    sv[u] = vec_scale(V, vv[u]);
-#pragma unroll
-    for (int j = 0; j < kIters; ++j) {
-      const double2* pq = reinterpret_cast<const double2*>(y + base + j * (2 * kT));
-      q[u][j] = (VAR & 1) ? ld_nt(pq) : *pq;
-    }
-  }
-  double acc[G];
-#pragma unroll
-  for (int u = 0; u < G; ++u) {
-    acc[u] = 0.0;
-#pragma unroll
-    for (int j = 0; j < kIters; ++j) {
-      acc[u] = acc[u] + wr[2 * j] * (q[u][j].x * sv[u]);
-      acc[u] = acc[u] + wr[2 * j + 1] * (q[u][j].y * sv[u]);
-    }
-  }
-#pragma unroll
-  for (int u = 0; u < G; ++u) {
-    acc[u] = wave_butterfly(acc[u]);
-    if (lane == 0) red[vv[u]][wv] = acc[u];
-  }
-}
-
-// Stage 1: workgroup c reduces chunk c of every vector: lane t accumulates its
-// elements base + j*512 + 2t, +1 (j = 0..7) in order, wave butterfly, then
-// (w0 + w1) + (w2 + w3).  partial[v * nchunks + c].  w stays in registers and
-// each vector streams 32 KiB contiguous per workgroup.
-// VAR: bit 0 = non-temporal loads of the basis vectors (the default: each
-// vector streams through once per kernel and is far larger than the 256 MiB
-// MALL, so caching it only evicts lines others still need; +8-16 % per kernel,
-// +7.7 % per GMRES step on 256^3, same-box A/B); bit 2 = non-temporal store
-// of w in MAXPY; bit 4 = vectors one at a time in MDot (A/B of the grouped loads).
-// Results are identical.
-template <int NV, bool SELF, int VAR, bool OPW = false>
-__device__ __forceinline__ void dot_chunk(const double* __restrict__ w, const Vecs& V, int64_t n,
-                                          double* __restrict__ partial, int64_t nchunks, int rev, int64_t c,
-                                          double (&red)[NV][4], const EllOp* op = nullptr,
-                                          const int32_t* sdel = nullptr, const double* sval = nullptr) {
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  const int64_t base = c * kChunk + 2 * t;
-  const bool full = (c + 1) * kChunk <= n;
-  double wr[2 * kIters];
-  if constexpr (OPW) {
-    ell_rows<0, kIters>(*op, sdel, sval, *op->sdev, base, n, wr);
-  } else if (full) {
-#pragma unroll
-    for (int j = 0; j < kIters; ++j) {
-      const double2 q = *reinterpret_cast<const double2*>(w + base + j * (2 * kT));
-      wr[2 * j] = q.x;
-      wr[2 * j + 1] = q.y;
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < kIters; ++j) {
-      const int64_t e = base + j * (2 * kT);
-      wr[2 * j] = e < n ? w[e] : 0.0;
-      wr[2 * j + 1] = e + 1 < n ? w[e + 1] : 0.0;
-    }
-  }
-  if (!SELF && full && (VAR & 16) == 0) {
-    constexpr int G = NV >= 4 ? 4 : NV;
-    int g = 0;
-    if constexpr ((VAR & 32) != 0) {  // two groups per iteration (MSK_TUNE_MDOT_UNROLL2)
-#pragma unroll 2
-      for (; g + G <= NV; g += G) dot_group_full<G, VAR>(wr, V, base, rev, NV, g, red, lane, wv);
-    } else {
-#pragma unroll 1
-      for (; g + G <= NV; g += G) dot_group_full<G, VAR>(wr, V, base, rev, NV, g, red, lane, wv);
-    }
-    if constexpr (NV % G == 3) dot_group_full<3, VAR>(wr, V, base, rev, NV, g, red, lane, wv);
-    if constexpr (NV % G == 2) dot_group_full<2, VAR>(wr, V, base, rev, NV, g, red, lane, wv);
-    if constexpr (NV % G == 1) dot_group_full<1, VAR>(wr, V, base, rev, NV, g, red, lane, wv);
-  } else {
-#pragma unroll
-  for (int vi = 0; vi < NV; ++vi) {
-    // load order only (each dot is independent): newest vector first when rev,
-    // so the CGS MAXPY that follows finds the oldest ones still in the MALL
-    const int v = rev ? NV - 1 - vi : vi;
-    double acc = 0.0;
-    if (SELF) {
-      if (full) {
-#pragma unroll
-        for (int j = 0; j < 2 * kIters; ++j) acc = acc + wr[j] * wr[j];
-      } else {
-#pragma unroll
-        for (int j = 0; j < kIters; ++j) {
-          const int64_t e = base + j * (2 * kT);
-          if (e < n) acc = acc + wr[2 * j] * wr[2 * j];
-          if (e + 1 < n) acc = acc + wr[2 * j + 1] * wr[2 * j + 1];
-        }
-      }
-    } else {
-      const double* __restrict__ y = vec_at(V, v);
-      const double sv = vec_scale(V, v);
-      if (full) {
-        double2 q[kIters];
-#pragma unroll
-        for (int j = 0; j < kIters; ++j) {
-          const double2* pq = reinterpret_cast<const double2*>(y + base + j * (2 * kT));
-          q[j] = (VAR & 1) ? ld_nt(pq) : *pq;
-        }
-#pragma unroll
-        for (int j = 0; j < kIters; ++j) {
-          acc = acc + wr[2 * j] * (q[j].x * sv);
-          acc = acc + wr[2 * j + 1] * (q[j].y * sv);
-        }
-      } else {
-#pragma unroll
-        for (int j = 0; j < kIters; ++j) {
-          const int64_t e = base + j * (2 * kT);
-          if (e < n) acc = acc + wr[2 * j] * (y[e] * sv);
-          if (e + 1 < n) acc = acc + wr[2 * j + 1] * (y[e + 1] * sv);
-        }
-      }
-    }
-    acc = wave_butterfly(acc);
-    if (lane == 0) red[v][wv] = acc;
-  }
-  }
-  __syncthreads();
-  if (t < NV) partial[t * nchunks + c] = (red[t][0] + red[t][1]) + (red[t][2] + red[t][3]);
-}
-
-template <int NV, bool SELF, int VAR>
-__global__ __launch_bounds__(kT) void k_dot_stage1(const double* __restrict__ w, Vecs V, int64_t n,
-                                                   double* __restrict__ partial, int64_t nchunks,
-                                                   const int* __restrict__ stop, int rev) {
-  if (stopped(stop)) return;
-  __shared__ double red[NV][4];
-  dot_chunk<NV, SELF, VAR>(w, V, n, partial, nchunks, rev, blockIdx.x, red);
-}
-
-// Stage 1 with W = A (sc x) computed in the kernel (no W vector in HBM).
-template <int NV, int VAR>
-__global__ __launch_bounds__(kT) void k_dot_stage1_op(EllOp op, Vecs V, int64_t n, double* __restrict__ partial,
-                                                      int64_t nchunks, const int* __restrict__ stop) {
-  __shared__ double red[NV][4];
-  __shared__ int32_t sdel[kT];
-  __shared__ double sval[kT];
-  ell_dict_stage(op, sdel, sval);
-  if (stopped(stop)) return;  // uniform: every lane reads the same flag
-  __syncthreads();
-  dot_chunk<NV, false, VAR, true>(nullptr, V, n, partial, nchunks, 0, blockIdx.x, red, &op, sdel, sval);
-}
-
-// Stage 2: workgroup v folds the nchunks partials of vector v the same way.
-template <bool HS>
-__global__ __launch_bounds__(kT) void k_dot_stage2(const double* __restrict__ partial, int64_t nchunks,
-                                                   double* __restrict__ out, const int* __restrict__ stop) {
-  // the stop flag (HS: stop is not null) is read together with the partials and tested after the
-  // (convergent) butterfly, so a running cycle waits for one round of loads, not two
-  bool skip = false;
-  if constexpr (HS) skip = *stop != 0;
-  __shared__ double red[4];
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  const double* p = partial + blockIdx.x * nchunks;
-  double acc = 0.0;
-  int64_t i = t;
-  // 16, then 8 loads in flight per lane, added in the same order (lane t: p[t], p[t+256], ...)
-  for (; i + 15 * kT < nchunks; i += 16 * kT) {
-    double q[16];
-#pragma unroll
-    for (int u = 0; u < 16; ++u) q[u] = p[i + u * kT];
-#pragma unroll
-    for (int u = 0; u < 16; ++u) acc = acc + q[u];
-  }
-  for (; i + 7 * kT < nchunks; i += 8 * kT) {
-    double q[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) q[u] = p[i + u * kT];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) acc = acc + q[u];
-  }
-  for (; i < nchunks; i += kT) acc = acc + p[i];
-  acc = wave_butterfly(acc);
-  if (skip) return;  // uniform
-  if (lane == 0) red[wv] = acc;
-  __syncthreads();
-  if (t == 0) out[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// ------------------------------------------------------------------ MAXPY
-// Vector-major MAXPY in the DBR chunk layout: workgroup c owns elements
-// [4096c, 4096c+4096); lane t owns base + j*512 + 2t, +1 (j = 0..7) and keeps
-// their 16 running values in registers while the vectors stream past group by
-// group (each group = up to 4 vectors x 32 KiB contiguous per workgroup).
-// Per element the arithmetic is PETSc VecMAXPY_Seq's: the nv&3 leading vectors
-// (PetscKernelAXPY3/2/1), then groups of four (PetscKernelAXPY4),
-// U += a0*p0 + a1*p1 + a2*p2 + a3*p3 evaluated left to right.
-// NORM: also the DBR partial of ||w_new||^2 for this chunk (VecNorm fused).
-template <int G>
-__device__ __forceinline__ double group_sum(const double (&a)[G], const double (&p)[G]) {
-  if constexpr (G == 1) {
-    return a[0] * p[0];
-  } else {
-    double s = a[0] * p[0] + a[1] * p[1];
-    if constexpr (G > 2) s = s + a[2] * p[2];
-    if constexpr (G > 3) s = s + a[3] * p[3];
-    return s;
-  }
-}
-
-template <int G, bool FULL, int VAR, int J0, int JN>
-__device__ __forceinline__ void chunk_group(double (&u)[2 * kIters], const Vecs& V, const Coefs& A,
-                                            const double* __restrict__ adev, int negate, int g, int64_t base,
-                                            int64_t n) {
-  double a[G], sv[G];
-  const double* vp[G];
-#pragma unroll
-  for (int q = 0; q < G; ++q) {  // wave-uniform: scalar loads from the kernel arguments / adev
-    const double aq = adev ? adev[g + q] : A.a[g + q];
-    a[q] = negate ? -aq : aq;
-    vp[q] = vec_at(V, g + q);
-    sv[q] = vec_scale(V, g + q);
-  }
-#pragma unroll
-  for (int j = J0; j < J0 + JN; ++j) {
-    const int64_t e = base + j * (2 * kT);
-    double p0[G], p1[G];
-#pragma unroll
-    for (int q = 0; q < G; ++q) {
-      if (FULL) {
-        const double2* pv = reinterpret_cast<const double2*>(vp[q] + e);
-        const double2 v = (VAR & 1) ? ld_nt(pv) : *pv;
-        p0[q] = v.x * sv[q];
-        p1[q] = v.y * sv[q];
-      } else {
-        p0[q] = e < n ? vp[q][e] * sv[q] : 0.0;
-        p1[q] = e + 1 < n ? vp[q][e + 1] * sv[q] : 0.0;
-      }
-    }
-    const double s0 = group_sum<G>(a, p0), s1 = group_sum<G>(a, p1);
-    if constexpr (G == 1) {  // PetscKernelAXPY: s = a*p; s += U
-      u[2 * j] = s0 + u[2 * j];
-      u[2 * j + 1] = s1 + u[2 * j + 1];
-    } else {
-      u[2 * j] = u[2 * j] + s0;
-      u[2 * j + 1] = u[2 * j + 1] + s1;
-    }
-  }
-}
-
-// One slice [J0, J0+JN) of the lane's 8 double2 positions: load w, run every
-// vector group over it, store and add its squares to acc in j order.  The
-// chunk is one slice (VAR bit 3 clear) or two halves one after the other (set:
-// half the registers, twice the waves per SIMD); per element nothing changes.
-template <bool ACCUM, bool NORM, bool FULL, int VAR, int J0, int JN, bool OPW = false>
-__device__ __forceinline__ void maxpy_slice(const double* __restrict__ win, double* __restrict__ wout,
-                                            const Vecs& V, const Coefs& A, const double* __restrict__ adev,
-                                            int negate, int nv, int64_t base, int64_t n, double& acc,
-                                            const EllOp* op = nullptr, const int32_t* sdel = nullptr,
-                                            const double* sval = nullptr) {
-  double u[2 * kIters];
-  if constexpr (OPW) {
-    ell_rows<J0, JN>(*op, sdel, sval, *op->sdev, base, n, u);
-  } else {
-#pragma unroll
-    for (int j = J0; j < J0 + JN; ++j) {
-      const int64_t e = base + j * (2 * kT);
-      if (ACCUM) {
-        u[2 * j] = 0.0;
-        u[2 * j + 1] = 0.0;
-      } else if (FULL) {
-        const double2 q = *reinterpret_cast<const double2*>(win + e);
-        u[2 * j] = q.x;
-        u[2 * j + 1] = q.y;
-      } else {
-        u[2 * j] = e < n ? win[e] : 0.0;
-        u[2 * j + 1] = e + 1 < n ? win[e + 1] : 0.0;
-      }
-    }
-  }
-  const int jrem = nv & 3;
-  if (jrem == 3) chunk_group<3, FULL, VAR, J0, JN>(u, V, A, adev, negate, 0, base, n);
-  else if (jrem == 2) chunk_group<2, FULL, VAR, J0, JN>(u, V, A, adev, negate, 0, base, n);
-  else if (jrem == 1) chunk_group<1, FULL, VAR, J0, JN>(u, V, A, adev, negate, 0, base, n);
-  if constexpr ((VAR & 32) != 0) {  // two groups per iteration: the compiler issues 8 vectors' loads at once
-#pragma unroll 2
-    for (int g = jrem; g < nv; g += 4) chunk_group<4, FULL, VAR, J0, JN>(u, V, A, adev, negate, g, base, n);
-  } else {
-#pragma unroll 1
-    for (int g = jrem; g < nv; g += 4) chunk_group<4, FULL, VAR, J0, JN>(u, V, A, adev, negate, g, base, n);
-  }
-#pragma unroll
-  for (int j = J0; j < J0 + JN; ++j) {
-    const int64_t e = base + j * (2 * kT);
-    double r0 = u[2 * j], r1 = u[2 * j + 1];
-    if (FULL) {
-      if (ACCUM) {  // VecAXPY(x, 1.0, T): x + T
-        const double2 q = *reinterpret_cast<const double2*>(win + e);
-        r0 = q.x + r0;
-        r1 = q.y + r1;
-      }
-      if constexpr ((VAR & 4) != 0) {
-        dx2 o;
-        o.x = r0;
-        o.y = r1;
-        __builtin_nontemporal_store(o, reinterpret_cast<dx2*>(wout + e));
-      } else {
-        *reinterpret_cast<double2*>(wout + e) = make_double2(r0, r1);
-      }
-      if (NORM) {
-        acc = acc + r0 * r0;
-        acc = acc + r1 * r1;
-      }
-    } else {
-      if (e < n) {
-        if (ACCUM) r0 = win[e] + r0;
-        wout[e] = r0;
-        if (NORM) acc = acc + r0 * r0;
-      }
-      if (e + 1 < n) {
-        if (ACCUM) r1 = win[e + 1] + r1;
-        wout[e + 1] = r1;
-        if (NORM) acc = acc + r1 * r1;
-      }
-    }
-  }
-}
-
-template <bool ACCUM, bool NORM, bool FULL, int VAR, bool OPW = false>
-__device__ __forceinline__ void maxpy_chunk_body(const double* __restrict__ win, double* __restrict__ wout,
-                                                 const Vecs& V, const Coefs& A, const double* __restrict__ adev,
-                                                 int negate, int nv, int64_t base, int64_t n, double& sq,
-                                                 const EllOp* op = nullptr, const int32_t* sdel = nullptr,
-                                                 const double* sval = nullptr) {
-  double acc = 0.0;
-  if constexpr ((VAR & 8) != 0) {
-    maxpy_slice<ACCUM, NORM, FULL, VAR, 0, kIters / 2, OPW>(win, wout, V, A, adev, negate, nv, base, n, acc, op,
-                                                            sdel, sval);
-    maxpy_slice<ACCUM, NORM, FULL, VAR, kIters / 2, kIters / 2, OPW>(win, wout, V, A, adev, negate, nv, base, n,
-                                                                     acc, op, sdel, sval);
-  } else {
-    maxpy_slice<ACCUM, NORM, FULL, VAR, 0, kIters, OPW>(win, wout, V, A, adev, negate, nv, base, n, acc, op, sdel,
-                                                        sval);
-  }
-  sq = acc;
-}
-
-template <bool ACCUM, bool NORM, int VAR>
-__global__ __launch_bounds__(kT) void k_maxpy_chunk(const double* win, double* wout, Vecs V, Coefs A,
-                                                    const double* __restrict__ adev, int negate, int nv,
-                                                    const int* __restrict__ nvdev, int64_t n,
-                                                    double* __restrict__ partial, const int* __restrict__ stop) {
-  if (stopped(stop)) return;
-  if (nvdev) nv = *nvdev;
-  if (nv <= 0) return;
-  const int t = threadIdx.x;
-  const int64_t c = (VAR & 64) ? (int64_t)gridDim.x - 1 - blockIdx.x : blockIdx.x;  // 64: top chunks first
-  const int64_t base = c * kChunk + 2 * t;
-  double sq = 0.0;
-  if ((c + 1) * kChunk <= n) maxpy_chunk_body<ACCUM, NORM, true, VAR>(win, wout, V, A, adev, negate, nv, base, n, sq);
-  else maxpy_chunk_body<ACCUM, NORM, false, VAR>(win, wout, V, A, adev, negate, nv, base, n, sq);
-  if (NORM) {
-    __shared__ double red[4];
-    sq = wave_butterfly(sq);
-    if ((t & 63) == 0) red[t >> 6] = sq;
-    __syncthreads();
-    if (t == 0) partial[c] = (red[0] + red[1]) + (red[2] + red[3]);
-  }
-}
-
-// CGS VecMAXPY with W = A (sc x) computed in the kernel, and the ||w||^2 partials.
-template <int VAR>
-__global__ __launch_bounds__(kT) void k_maxpy_op(EllOp op, double* wout, Vecs V, const double* __restrict__ adev,
-                                                 int nv, int64_t n, double* __restrict__ partial,
-                                                 const int* __restrict__ stop) {
-  __shared__ int32_t sdel[kT];
-  __shared__ double sval[kT];
-  __shared__ double red[4];
-  ell_dict_stage(op, sdel, sval);
-  if (stopped(stop)) return;  // uniform
-  __syncthreads();
-  const int t = threadIdx.x;
-  const int64_t c = blockIdx.x;
-  const int64_t base = c * kChunk + 2 * t;
-  const Coefs A = {};
-  double sq = 0.0;
-  if ((c + 1) * kChunk <= n)
-    maxpy_chunk_body<false, true, true, VAR, true>(nullptr, wout, V, A, adev, 1, nv, base, n, sq, &op, sdel, sval);
-  else
-    maxpy_chunk_body<false, true, false, VAR, true>(nullptr, wout, V, A, adev, 1, nv, base, n, sq, &op, sdel, sval);
-  sq = wave_butterfly(sq);
-  if ((t & 63) == 0) red[t >> 6] = sq;
-  __syncthreads();
-  if (t == 0) partial[c] = (red[0] + red[1]) + (red[2] + red[3]);
-}
+namespace {  // internal linkage: the kernels are launched from this file only
 
 // ------------------------------------------------------------------- SpMV
 // Row-blocked CSR: workgroup b owns rows [256b, 256b+256).  Its contiguous
@@ -2784,8 +2269,7 @@ __global__ __launch_bounds__(kT) void k_blas1(double* __restrict__ y, const doub
 // ===================================================================== launchers
 using namespace msk;
 
-// Tuning flags (A/B experiments; MSPLIT_TUNING at context creation), defined once (the MISC part).
-#if MSK_IN(MSK_PART_MISC)
+// Tuning flags (A/B experiments; MSPLIT_TUNING at context creation); the other units read them (msplit_kdev.hpp).
 __attribute__((visibility("hidden"))) int msk_tuning_flags = 0;
 __attribute__((visibility("hidden"))) int msk_spmv_gb_override = 0;  // XCD group size override (0: auto)
 __attribute__((visibility("hidden"))) int msk_march_z_override = 0;  // z-march planes per workgroup (0: auto)
@@ -2819,15 +2303,8 @@ extern "C" void msk_set_gm_wfree(int on) {
   ++msk_shape_epoch;
 }
 extern "C" int msk_get_gm_wfree(void) { return msk_gm_wfree; }
-#else
-extern __attribute__((visibility("hidden"))) int msk_tuning_flags;
-extern __attribute__((visibility("hidden"))) int msk_spmv_gb_override;
-extern __attribute__((visibility("hidden"))) int msk_march_z_override;
-extern __attribute__((visibility("hidden"))) int msk_march_lines_override;
-extern __attribute__((visibility("hidden"))) int msk_gm_wfree;
-#endif
 
-[[maybe_unused]] static inline XcdMap xcd_map(int32_t nrows, int64_t plane) {
+static inline XcdMap xcd_map(int32_t nrows, int64_t plane) {
   XcdMap m = {0, 0, 0};
   if (msk_tuning_flags & MSK_TUNE_SPMV_ZCHUNK) {  // A/B: each XCD a contiguous eighth of the rows
     const int32_t nblk = (nrows + kT - 1) / kT;
@@ -2847,166 +2324,13 @@ extern __attribute__((visibility("hidden"))) int msk_gm_wfree;
   return m;
 }
 
-[[maybe_unused]] static inline int grid_for(int64_t work, int cap) {
+static inline int grid_for(int64_t work, int cap) {
   int64_t g = (work + kT - 1) / kT;
   if (g < 1) g = 1;
   if (g > cap) g = cap;
   return (int)g;
 }
 
-// basis-vector load policy: non-temporal unless MSK_TUNE_VEC_TEMPORAL (A/B)
-[[maybe_unused]] static inline int vec_var() { return (msk_tuning_flags & MSK_TUNE_VEC_TEMPORAL) ? 0 : 1; }
-
-__attribute__((visibility("hidden"))) int msk_dot1_variants_a(int var, int nv, const double* w, const Vecs& V,
-                                                               int64_t n, double* partial, int64_t nchunks,
-                                                               const int* stop, hipStream_t s);
-__attribute__((visibility("hidden"))) int msk_dot1_variants_b(int var, int nv, const double* w, const Vecs& V,
-                                                               int64_t n, double* partial, int64_t nchunks,
-                                                               const int* stop, hipStream_t s);
-
-template <int NV, int VAR>
-static void dot1_dispatch(int nv, const double* w, const Vecs& V, int64_t n, double* partial, int64_t nchunks,
-                          const int* stop, hipStream_t s) {
-  if (nv == NV) {
-    k_dot_stage1<NV, false, VAR><<<dim3((unsigned)nchunks), dim3(kT), 0, s>>>(
-        w, V, n, partial, nchunks, stop, (msk_tuning_flags & MSK_TUNE_MDOT_REV) ? 1 : 0);
-  } else if constexpr (NV < MSK_MAX_GROUP) {
-    dot1_dispatch<NV + 1, VAR>(nv, w, V, n, partial, nchunks, stop, s);
-  }
-}
-
-#if MSK_IN(MSK_PART_DOT)
-extern "C" int msk_dot_stage1(const double* w, const Vecs* V, int nv, int64_t n, double* partial, int64_t nchunks,
-                              int self, const int* stop, hipStream_t s) {
-  if (nchunks <= 0) return 0;
-  if (!self && (nv < 1 || nv > MSK_MAX_GROUP)) return (int)hipErrorInvalidValue;
-  const int var = vec_var() | ((msk_tuning_flags & MSK_TUNE_MDOT_SINGLE) ? 16 : 0) |
-                  ((msk_tuning_flags & MSK_TUNE_MDOT_UNROLL2) ? 32 : 0);
-  if (self)
-    k_dot_stage1<1, true, 0><<<dim3((unsigned)nchunks), dim3(kT), 0, s>>>(w, *V, n, partial, nchunks, stop, 0);
-  else if (var == 1) dot1_dispatch<1, 1>(nv, w, *V, n, partial, nchunks, stop, s);
-  else if (msk_dot1_variants_a(var, nv, w, *V, n, partial, nchunks, stop, s) &&
-           msk_dot1_variants_b(var, nv, w, *V, n, partial, nchunks, stop, s))
-    return (int)hipErrorInvalidValue;  // a tuning combination with no kernel: fail, never run another one
-  return (int)hipGetLastError();
-}
-#endif  // part
-
-// The A/B variants of the MDot kernel, in parts of their own (each variant is 32 instantiations).
-// Return 0 when they launched the variant, 1 when it is not theirs.
-#if MSK_IN(MSK_PART_DOT_A)
-int msk_dot1_variants_a(int var, int nv, const double* w, const Vecs& V, int64_t n, double* partial,
-                        int64_t nchunks, const int* stop, hipStream_t s) {
-  if (var == 0) dot1_dispatch<1, 0>(nv, w, V, n, partial, nchunks, stop, s);
-  else if (var == 16) dot1_dispatch<1, 16>(nv, w, V, n, partial, nchunks, stop, s);
-  else return 1;
-  return 0;
-}
-#endif  // part
-#if MSK_IN(MSK_PART_DOT_B)
-int msk_dot1_variants_b(int var, int nv, const double* w, const Vecs& V, int64_t n, double* partial,
-                        int64_t nchunks, const int* stop, hipStream_t s) {
-  if (var == 17) dot1_dispatch<1, 17>(nv, w, V, n, partial, nchunks, stop, s);
-  else if (var == 32) dot1_dispatch<1, 32>(nv, w, V, n, partial, nchunks, stop, s);
-  else if (var == 33) dot1_dispatch<1, 33>(nv, w, V, n, partial, nchunks, stop, s);
-  else return 1;
-  return 0;
-}
-#endif  // part
-#if MSK_IN(MSK_PART_DOT)
-
-template <int NV, int VAR>
-static void dot1_op_dispatch(int nv, const EllOp& op, const Vecs& V, int64_t n, double* partial, int64_t nchunks,
-                             const int* stop, hipStream_t s) {
-  if (nv == NV) {
-    k_dot_stage1_op<NV, VAR><<<dim3((unsigned)nchunks), dim3(kT), 0, s>>>(op, V, n, partial, nchunks, stop);
-  } else if constexpr (NV < MSK_MAX_GROUP) {
-    dot1_op_dispatch<NV + 1, VAR>(nv, op, V, n, partial, nchunks, stop, s);
-  }
-}
-
-extern "C" int msk_dot_stage1_op(const EllOp* op, const Vecs* V, int nv, int64_t n, double* partial,
-                                 int64_t nchunks, const int* stop, hipStream_t s) {
-  if (nchunks <= 0) return 0;
-  if (nv < 1 || nv > MSK_MAX_GROUP || op->ndict > 255) return (int)hipErrorInvalidValue;
-  if (vec_var()) dot1_op_dispatch<1, 1>(nv, *op, *V, n, partial, nchunks, stop, s);
-  else dot1_op_dispatch<1, 0>(nv, *op, *V, n, partial, nchunks, stop, s);
-  return (int)hipGetLastError();
-}
-#endif  // part
-
-#if MSK_IN(MSK_PART_MAXPY)
-extern "C" int msk_maxpy_op(const EllOp* op, double* wout, const Vecs* V, int nv, const double* adev, int64_t n,
-                            double* partial, const int* stop, hipStream_t s) {
-  if (n <= 0 || nv <= 0) return 0;
-  if (op->ndict > 255) return (int)hipErrorInvalidValue;
-  const unsigned g = (unsigned)((n + kChunk - 1) / kChunk);
-  const int var = vec_var() | ((msk_tuning_flags & MSK_TUNE_MAXPY_TEMPORAL_ST) ? 0 : 4);
-  if (var == 5) k_maxpy_op<5><<<g, kT, 0, s>>>(*op, wout, *V, adev, nv, n, partial, stop);
-  else if (var == 4) k_maxpy_op<4><<<g, kT, 0, s>>>(*op, wout, *V, adev, nv, n, partial, stop);
-  else if (var == 1) k_maxpy_op<1><<<g, kT, 0, s>>>(*op, wout, *V, adev, nv, n, partial, stop);
-  else k_maxpy_op<0><<<g, kT, 0, s>>>(*op, wout, *V, adev, nv, n, partial, stop);
-  return (int)hipGetLastError();
-}
-#endif  // part
-
-#if MSK_IN(MSK_PART_DOT)
-extern "C" int msk_dot_stage2(const double* partial, int64_t nchunks, int nv, double* out, const int* stop,
-                              hipStream_t s) {
-  if (stop) k_dot_stage2<true><<<dim3(nv), dim3(kT), 0, s>>>(partial, nchunks, out, stop);
-  else k_dot_stage2<false><<<dim3(nv), dim3(kT), 0, s>>>(partial, nchunks, out, nullptr);
-  return (int)hipGetLastError();
-}
-#endif  // part
-
-#if MSK_IN(MSK_PART_MAXPY)
-extern "C" int msk_maxpy_chunk(const double* win, double* wout, const Vecs* V, int nv, const int* nvdev,
-                               const Coefs* A, const double* adev, int negate, int64_t n, int accum, double* partial,
-                               const int* stop, hipStream_t s) {
-  if (n <= 0 || (nv <= 0 && !nvdev)) return 0;
-  // non-temporal store of w too unless MSK_TUNE_MAXPY_TEMPORAL_ST (+0.4 % per step); the group loop
-  // unrolled by two unless MSK_TUNE_MAXPY_UNROLL1 (+1.7 % per step: 64-load bursts at one wave per SIMD)
-  const int var = vec_var() | ((msk_tuning_flags & MSK_TUNE_MAXPY_TEMPORAL_ST) ? 0 : 4) |
-                  ((msk_tuning_flags & MSK_TUNE_MAXPY_HALVES) ? 8 : 0) | ((msk_tuning_flags & MSK_TUNE_MAXPY_UNROLL1) ? 0 : 32);
-  // Top chunk first where a vector outgrows the 256 MiB MALL (n > 2^25): MAXPY then starts on the rows the
-  // fused MatMult+MDot (or the MDot) left in the MALL and ends on those the next one starts with (SMSM's
-  // 512x512x256 block +1.0 %, MAXPY 5.68 -> 5.86 TB/s; at 256^3, where whole vectors fit, -0.7 %; same box,
-  // profiles/r03/rev_ab/).  MSPLIT_MAXPY_REV=0/1 forces either order.
-  static const int rev_env = [] {
-    const char* e = getenv("MSPLIT_MAXPY_REV");
-    return e ? (atoi(e) ? 1 : 0) : -1;
-  }();
-  const int rev = (rev_env < 0 ? n > ((int64_t)1 << 25) : rev_env) ? 64 : 0;
-  const unsigned g = (unsigned)((n + kChunk - 1) / kChunk);
-#define MSK_MAXPY_LAUNCH(V_)                                                                                     \
-  if (partial)                                                                                                  \
-    k_maxpy_chunk<false, true, V_><<<dim3(g), dim3(kT), 0, s>>>(win, wout, *V, *A, adev, negate, nv, nvdev, n,   \
-                                                                partial, stop);                                \
-  else if (accum)                                                                                               \
-    k_maxpy_chunk<true, false, V_><<<dim3(g), dim3(kT), 0, s>>>(win, wout, *V, *A, adev, negate, nv, nvdev, n,   \
-                                                                partial, stop);                                \
-  else                                                                                                          \
-    k_maxpy_chunk<false, false, V_><<<dim3(g), dim3(kT), 0, s>>>(win, wout, *V, *A, adev, negate, nv, nvdev, n,  \
-                                                                 partial, stop);
-  switch (var) {
-    case 0: MSK_MAXPY_LAUNCH(0) break;
-    case 1: MSK_MAXPY_LAUNCH(1) break;
-    case 4: MSK_MAXPY_LAUNCH(4) break;
-    case 5: MSK_MAXPY_LAUNCH(5) break;
-    case 13: MSK_MAXPY_LAUNCH(13) break;
-    case 32: MSK_MAXPY_LAUNCH(32) break;
-    case 33: if (rev) { MSK_MAXPY_LAUNCH(97) } else { MSK_MAXPY_LAUNCH(33) } break;
-    case 36: MSK_MAXPY_LAUNCH(36) break;
-    case 37: if (rev) { MSK_MAXPY_LAUNCH(101) } else { MSK_MAXPY_LAUNCH(37) } break;
-    case 45: MSK_MAXPY_LAUNCH(45) break;
-    default: return (int)hipErrorInvalidValue;  // a tuning combination with no kernel: fail, never run another one
-  }
-#undef MSK_MAXPY_LAUNCH
-  return (int)hipGetLastError();
-}
-#endif  // part
-
-#if MSK_IN(MSK_PART_SPMV)
 extern "C" int msk_spmv(int32_t nrows, const int32_t* rowptr, const int32_t* col, const double* val, const double* x,
                         const double* b, double* y, int32_t lds_cap, int mode, const double* sdev, double* vout,
                         const int* stop, int64_t plane, hipStream_t s) {
@@ -3604,9 +2928,7 @@ extern "C" int msk_spmv_rows(int32_t nlisted, const int32_t* row_ids, const int3
   else k_spmv_rows<false><<<dim3(g), dim3(kT), 0, s>>>(nlisted, row_ids, rowptr, col, val, x, b, y);
   return (int)hipGetLastError();
 }
-#endif  // part
 
-#if MSK_IN(MSK_PART_MISC)
 extern "C" int msk_box_stencil(int dim, int32_t nx, int32_t ny, int32_t nz, int64_t nrows, int lo, int hi,
                                const BoxCoef* cf, int32_t* rowptr, int32_t* col, double* val, hipStream_t s) {
   const int g = grid_for(nrows + 1, 8192);
@@ -3648,4 +2970,3 @@ extern "C" int msk_blas1(int op, double* y, const double* x, const double* z, do
   }
   return (int)hipGetLastError();
 }
-#endif  // part

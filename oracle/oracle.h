@@ -51,7 +51,7 @@ enum { ORC_REDUCE_SEQ = 0, ORC_REDUCE_DBR = 1, ORC_REDUCE_MT = 2 };
  * order with one rank per thread. */
 void orc_set_threads(int threads);
 
-/* DBR geometry -- must match csrc/msplit_kernels.hip */
+/* DBR geometry -- must match csrc/msplit_kdev.hpp */
 #define ORC_DBR_THREADS 256
 #define ORC_DBR_VW 2
 #define ORC_DBR_ITERS 8
