@@ -228,7 +228,18 @@ int msp_mat_residual_listed(msp_mat *A, const msp_vec *b, const msp_vec *x, msp_
 /* -------------------------------------------------------------------- Vec */
 /* VecCreate/VecSetSizes/VecSetType (utils.c:157-168): zero-initialised, in HBM. */
 int msp_vec_create(msp_ctx *ctx, int64_t n, msp_vec **v);
-/* Wrap caller-owned device memory (VecCreateSeqWithArray analogue); not freed. */
+/* Wrap caller-owned device memory (VecCreateSeqWithArray analogue); not freed.
+ * What every kernel assumes of a vector, owned or wrapped, and all it assumes:
+ *  - device_ptr is 16-byte aligned (checked here; anything else is MSP_ERR_ARG_WRONG).  No more: a wrapped
+ *    vector need not be 32-byte or 4 KiB aligned as an owned one is.  The widest load or store applied to a
+ *    vector is 16 bytes (two doubles); a kernel that pairs elements does so from an even index.
+ *  - Elements [0, n) are read and written.  A kernel may also READ up to 512 doubles past n rounded up to
+ *    even -- the slack msp_vec_create allocates behind an owned vector, and the 512 doubles a dense block keeps
+ *    behind its last column (msp_dense_get_array + column offset) -- so that much must be addressable; what is
+ *    read there never reaches a result, whatever it holds (NaN included).  Nothing before device_ptr is touched.
+ *  - Nothing at or past n is ever WRITTEN, and every operation documented to set all of a vector writes each
+ *    of its n elements (MatMult writes the 0.0 of an empty row).
+ * tests/test_gpu_guarded.py runs every kernel family on vectors that give exactly this and no more. */
 int msp_vec_create_with_array(msp_ctx *ctx, int64_t n, double *device_ptr, msp_vec **v);
 int msp_vec_destroy(msp_vec **v);
 int msp_vec_get_size(const msp_vec *v, int64_t *n);

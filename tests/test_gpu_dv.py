@@ -171,10 +171,12 @@ def test_gmres_on_dv_equals_csr_and_oracle(ctx, oracle, dim, nx, ny, nz, restart
 @pytest.mark.parametrize("assembly,product", [(0, 8192), (0, 16384), (0, 0),            # ELL: 1, 2, 4 rows per lane
                                               (32768, 32768 | 8192), (32768, 32768 | 16384),
                                               (32768, 32768)])                         # CSR-order codes
-@pytest.mark.parametrize("case", ["box", "banded", "ragged-tail", "w4", "w16", "long-rows"])
+@pytest.mark.parametrize("case", ["box", "banded", "ragged-tail", "w4", "w8", "w16", "long-rows"])
 def test_layout_and_rows_per_lane_variants_bitwise(ctx, oracle, assembly, product, case):
     """Each DV layout (ELL of 4/8/16 codes per row, or CSR-order codes with row lengths) and each
-    rows-per-lane variant against the oracle."""
+    rows-per-lane variant against the oracle.  ELL of 4: w4; of 8: box and w8; of 16: w16.  `banded` and
+    `ragged-tail` drop so many entries that padding to 8 codes would add more than half of them, and long-rows
+    exceeds 16 per row: dv_build keeps CSR-order codes for those whatever the assembly flag."""
     import ctypes
     from medane_tchakorom_ufc_thesis_repository_amd import _lib
     L = _lib.load()
@@ -182,6 +184,7 @@ def test_layout_and_rows_per_lane_variants_bitwise(ctx, oracle, assembly, produc
     L.msk_set_tuning.restype = None
     r = np.random.default_rng(SEED)
     offsets = {"banded": [-40, -1, 0, 2, 33], "ragged-tail": [-40, -1, 0, 2, 33], "w4": [-7, 0, 1],
+               "w8": [-40, -1, 0, 2, 33],
                "w16": [-900, -64, -9, -8, -3, -2, -1, 0, 1, 2, 3, 8, 64, 900],
                "long-rows": list(range(-20, 21))}
     try:
@@ -193,9 +196,11 @@ def test_layout_and_rows_per_lane_variants_bitwise(ctx, oracle, assembly, produc
         else:
             nr = nc = 1024 * 3 + (517 if case == "ragged-tail" else 0)
             rp, col, val = _banded(nr, offsets[case], [-1.0, 4.0, 0.5], r,
-                                   drop=0.9 if case == "ragged-tail" else 0.3)
+                                   drop=0.9 if case == "ragged-tail" else 0.1 if case == "w8" else 0.3)
             A = Mat.from_csr(ctx, nr, nc, rp, col, val)
         assert A.get_storage() == "dv"
+        ell = not assembly and case in ("box", "w4", "w8", "w16")
+        assert A.spmv_kernel() == ("k_spmv_ell" if ell else "k_spmv_dv")
         O = oracle.Mat.from_arrays(nr, nc, rp, col, val)
         L.msk_set_tuning(product)
         _products(ctx, A, O, r)
