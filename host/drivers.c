@@ -200,13 +200,15 @@ static int ksp_from_options(msp_ksp *k, const msd_options *o, const char *p, msp
   if (opt_bool(o, p, "ksp_converged_use_initial_residual_norm", 0)) ko->uirnorm = 1;
   if (msd_opt_has(o, p, "ksp_initial_guess_nonzero")) ko->guess_nonzero = opt_bool(o, p, "ksp_initial_guess_nonzero", 0);
   CK(msp_ksp_set_opts(k, ko));
-  /* -<prefix>msplit_basis_precision double|single: the Krylov basis stored as float (msp_ksp_set_basis_precision) */
+  /* -<prefix>msplit_basis_precision double|single|block16: the Krylov basis stored as float, or as int16 with one
+   * exponent per DBR chunk (msp_ksp_set_basis_precision) */
   const char *bp = msd_opt_str(o, p, "msplit_basis_precision", NULL);
   if (bp) {
     if (!strcasecmp(bp, "single")) CK(msp_ksp_set_basis_precision(k, MSP_BASIS_F32));
     else if (!strcasecmp(bp, "double")) CK(msp_ksp_set_basis_precision(k, MSP_BASIS_F64));
+    else if (!strcasecmp(bp, "block16")) CK(msp_ksp_set_basis_precision(k, MSP_BASIS_B16));
     else {
-      fprintf(stderr, "-%smsplit_basis_precision %s: expected double or single\n", p, bp);
+      fprintf(stderr, "-%smsplit_basis_precision %s: expected double, single or block16\n", p, bp);
       return MSP_ERR_ARG_OUTOFRANGE;
     }
   }

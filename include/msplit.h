@@ -296,7 +296,7 @@ int msp_ksp_get_residual_norm(const msp_ksp *ksp, double *rnorm);     /* KSPGetR
 int msp_ksp_get_converged_reason(const msp_ksp *ksp, int32_t *reason);
 /* Residual history of the last solve (KSPGetResidualHistory): its+1 entries. */
 int msp_ksp_get_residual_history(const msp_ksp *ksp, const double **hist, int32_t *n);
-/* Storage precision of the Krylov basis in HBM (-msplit_basis_precision double|single).
+/* Storage precision of the Krylov basis in HBM (-msplit_basis_precision double|single|block16).
  * MSP_BASIS_F64 (default): the basis is stored as double.
  * MSP_BASIS_F32: compressed-basis GMRES.  Each basis vector is rounded to float once, when it is stored
  * (round to nearest even, gradual underflow, overflow to +-inf), promoted to double as it is read, and its norm
@@ -304,9 +304,26 @@ int msp_ksp_get_residual_history(const msp_ksp *ksp, const double **hist, int32_
  * double, and every restart recomputes the true residual in double.  Half the basis bytes per step and per
  * block.  Entries beyond float range end the solve with MSP_DIVERGED_NANORINF.  DBR reduction only: a solve on a
  * context in MSP_REDUCE_SEQ returns MSP_ERR_SUP.  Changing the precision frees the work of an earlier set-up.
+ * MSP_BASIS_B16 (block16): block-scaled basis.  Each basis vector is stored as 16-bit integers with one shared
+ * power-of-two exponent per DBR chunk c (elements [4096c, min(4096(c+1), n))): two bytes per entry.  The rounding,
+ * applied once when a vector is stored, is per chunk:
+ *   - any entry NaN or +-inf: every entry of the chunk reads back NaN (the norm is NaN and the solve ends with
+ *     MSP_DIVERGED_NANORINF);
+ *   - M = max |v_i| == 0: every entry reads back +0.0;
+ *   - otherwise M = m 2^E with 0.5 <= m < 1 (frexp, subnormal M included),
+ *     q_i = clamp(rint(ldexp(v_i, 15 - E)), -32767, 32767) with ties to even, and the entry reads back
+ *     ldexp(q_i, E - 15): an absolute error of at most 2^-16 of the chunk's maximum (2^-15 where the clamp acts).
+ *   Range: the whole double exponent range (no float overflow or underflow).  Everything else is as for
+ *   MSP_BASIS_F32: norms are those of the values read back, every dot and sum, the Hessenberg and x stay double,
+ *   every restart recomputes the true residual in double, DBR reduction only (MSP_REDUCE_SEQ: MSP_ERR_SUP).
+ *   Limit: inside one restart cycle the recurrence residual can run ahead of the true residual by about 2^-13 of
+ *   the cycle's initial residual, so a tolerance is met reliably only across restarts.  block16 suits inexact inner
+ *   solves and fixed-iteration steps; a solve that must gain more than about three digits within a single cycle
+ *   wants MSP_BASIS_F32 or MSP_BASIS_F64.
  * Any other value: MSP_ERR_ARG_OUTOFRANGE. */
 #define MSP_BASIS_F64 0
 #define MSP_BASIS_F32 1
+#define MSP_BASIS_B16 2
 int msp_ksp_set_basis_precision(msp_ksp *ksp, int prec);
 int msp_ksp_get_basis_precision(const msp_ksp *ksp, int *prec);
 /* Device bytes the KSP holds once set up and solved with: the basis, W / the current vector, and the recurrence

@@ -40,9 +40,16 @@
  *            operator's scaled MatMult serves unchanged.  VV(it+1) = rnd(W - sum ...) is rounded when stored and
  *            its norm is the rounded values' norm; everything else is the same f64 arithmetic.  Neither opfuse nor
  *            wfree is taken, and the MDot / MAXPY variant flags of MSPLIT_TUNING do not apply.
+ *   block16  MSP_BASIS_B16: the f32 step with another stored format (msplit_cb16.hip): 16-bit integers with one
+ *            power-of-two exponent per DBR chunk and vector, the rounding rule of include/msplit.h.  Same launches,
+ *            same two f64 n-vectors, same arithmetic; the whole double exponent range is representable and a
+ *            non-finite entry ends the solve.  Inside one restart cycle the recurrence residual can run ahead of
+ *            the true one by about 2^-13 of the cycle's initial residual (the next restart recomputes it in f64):
+ *            for inexact inner solves and fixed-iteration steps, not for gaining many digits in a single cycle.
  *
  * Data layout: VV(0..min(m, max_it)) are one allocation of (min(m, max_it)+1) x stride elements; stride = n rounded
- * up to 512 doubles, or to 1024 floats (4 KiB either way).  W and the current vector are separate allocations.
+ * up to 512 doubles, to 1024 floats or to 2048 int16 (4 KiB each way); block16 keeps its int32 exponents,
+ * [vector][chunk], behind the last vector in the same allocation.  W and the current vector are separate allocations.
  * KSPInitialResidual writes VV(0) (f32: the current vector, which the cycle's first kernel rounds into VV(0)).
  */
 #include <math.h>
@@ -74,10 +81,13 @@ struct msp_ksp {
   msp_ksp_opts o;
   int setup;
   int64_t n, stride;
-  int basis_prec;           /* MSP_BASIS_F64 / MSP_BASIS_F32: the element type behind basis */
-  double *basis;            /* device: (m+1) * stride, stored unnormalised (scales in g.sc); floats when F32 */
+  int basis_prec;           /* MSP_BASIS_F64 / MSP_BASIS_F32 / MSP_BASIS_B16: the element type behind basis */
+  double *basis;            /* device: (m+1) * stride, stored unnormalised (scales in g.sc); floats when F32, int16
+                               followed by the exponent table when B16 */
+  int32_t *expo;            /* device, B16 only: exponents [vector][nchunks], inside the basis allocation */
+  int64_t nchunks;          /* DBR chunks per vector */
   double *tmp;              /* device: W = A VV(it) before the orthogonalisation */
-  double *cur;              /* device, F32 only: the newest basis vector's rounded values as doubles */
+  double *cur;              /* device, F32 / B16: the newest basis vector's rounded values as doubles */
   size_t basis_bytes, gblock_bytes, vec_bytes; /* sizes of the allocations (vec_bytes: tmp and cur, each) */
   mspi_gmres_dev g;         /* device-resident recurrence state and arrays */
   void *gblock;             /* the single device allocation behind g */
@@ -139,6 +149,7 @@ static void ksp_free_work(msp_ksp *k) {
   if (k->hst) mspi_host_free(k->hst);
   free(k->hist);
   k->basis = k->tmp = k->cur = NULL;
+  k->expo = NULL;
   k->basis_bytes = k->gblock_bytes = k->vec_bytes = 0;
   k->gblock = NULL;
   k->hst = NULL;
@@ -209,8 +220,9 @@ int msp_ksp_set_basis_precision(msp_ksp *k, int prec) {
     mspi_set_error(MSP_ERR_ARG_NULL, "NULL argument");
     return MSP_ERR_ARG_NULL;
   }
-  if (prec != MSP_BASIS_F64 && prec != MSP_BASIS_F32) {
-    mspi_set_error(MSP_ERR_ARG_OUTOFRANGE, "basis precision %d is neither MSP_BASIS_F64 nor MSP_BASIS_F32", prec);
+  if (prec != MSP_BASIS_F64 && prec != MSP_BASIS_F32 && prec != MSP_BASIS_B16) {
+    mspi_set_error(MSP_ERR_ARG_OUTOFRANGE,
+                   "basis precision %d is none of MSP_BASIS_F64, MSP_BASIS_F32, MSP_BASIS_B16", prec);
     return MSP_ERR_ARG_OUTOFRANGE;
   }
   if (prec != k->basis_prec && k->setup) { /* another element type: new work vectors, no graph survives */
@@ -252,15 +264,18 @@ int msp_ksp_set_up(msp_ksp *k) {
   const int64_t mv = (k->o.max_it < m ? k->o.max_it : m) + 1;
   int64_t skew = 0; /* an extra skew between basis vectors measured no gain (profiles/r01/skew_ab) */
   const char *env = getenv("MSPLIT_BASIS_SKEW");
-  const int f32 = k->basis_prec == MSP_BASIS_F32;
-  const int64_t align = f32 ? 1024 : 512; /* elements in 4 KiB */
+  const int f32 = k->basis_prec == MSP_BASIS_F32, b16 = k->basis_prec == MSP_BASIS_B16;
+  const int64_t align = b16 ? 2048 : f32 ? 1024 : 512; /* elements in 4 KiB */
   if (env) skew = (atoll(env) + align - 1) / align * align;
   k->stride = (k->n + align - 1) / align * align + skew;
   k->hist_cap = k->o.max_it + 2;
   /* one device block for the recurrence: state, then hh, cc, ss, grs, h, sc, hist */
   const size_t nd = (size_t)((m + 2) * (m + 1) + 5 * (m + 2) + k->hist_cap);
   const size_t st_bytes = (sizeof(mspi_gmres_state) + 63) / 64 * 64;
-  k->basis_bytes = (size_t)mv * (size_t)k->stride * (f32 ? sizeof(float) : sizeof(double)) + 4096;
+  const size_t elem = b16 ? sizeof(int16_t) : f32 ? sizeof(float) : sizeof(double);
+  const size_t vv_bytes = (size_t)mv * (size_t)k->stride * elem;
+  k->nchunks = (k->n + MSPI_DBR_CHUNK - 1) / MSPI_DBR_CHUNK;
+  k->basis_bytes = vv_bytes + (b16 ? (size_t)mv * (size_t)k->nchunks * sizeof(int32_t) : 0) + 4096;
   k->gblock_bytes = st_bytes + nd * sizeof(double);
   k->vec_bytes = (size_t)((k->n + 511) / 512 * 512) * sizeof(double) + 4096;
   int rc = mspi_malloc(k->ctx, (void **)&k->basis, k->basis_bytes);
@@ -276,6 +291,7 @@ int msp_ksp_set_up(msp_ksp *k) {
     ksp_free_work(k);
     return rc;
   }
+  k->expo = b16 ? (int32_t *)((char *)k->basis + vv_bytes) : NULL;
   double *d = (double *)((char *)k->gblock + st_bytes);
   k->g.st = (mspi_gmres_state *)k->gblock;
   k->g.hh = d;
@@ -297,12 +313,15 @@ int msp_ksp_set_up(msp_ksp *k) {
 
 static double *VV(const msp_ksp *k, int j) { return k->basis + (int64_t)j * k->stride; }
 static float *VF(const msp_ksp *k, int j) { return (float *)k->basis + (int64_t)j * k->stride; } /* MSP_BASIS_F32 */
+static int16_t *VH(const msp_ksp *k, int j) { return (int16_t *)k->basis + (int64_t)j * k->stride; } /* MSP_BASIS_B16 */
+static int32_t *EX(const msp_ksp *k, int j) { return k->expo + (int64_t)j * k->nchunks; }
+static int compressed(const msp_ksp *k) { return k->basis_prec != MSP_BASIS_F64; }
 
 /* Which Arnoldi step a cycle runs: the operator computed inside MDot and MAXPY (opfuse), the W-free step on a box
  * stencil (wfree), or W stored between the MatMult and the CGS kernels (neither).  The W-free choice follows the
  * operator and msk_set_gm_wfree, so it is asked again before every solve. */
 static void step_kind(const msp_ksp *k, int *opfuse, int *wfree) {
-  if (k->basis_prec == MSP_BASIS_F32) { /* those kernels read an f64 basis: the f32 step stores W */
+  if (compressed(k)) { /* those kernels read an f64 basis: the f32 / block16 step stores W */
     *opfuse = *wfree = 0;
     return;
   }
@@ -319,7 +338,7 @@ static int ensure_w(msp_ksp *k) {
   int rc = MSP_SUCCESS;
   if (!k->tmp) rc = mspi_malloc(k->ctx, (void **)&k->tmp, k->vec_bytes);
   /* the f32 step's second f64 n-vector: the MatMult's input */
-  if (!rc && k->basis_prec == MSP_BASIS_F32 && !k->cur) rc = mspi_malloc(k->ctx, (void **)&k->cur, k->vec_bytes);
+  if (!rc && compressed(k) && !k->cur) rc = mspi_malloc(k->ctx, (void **)&k->cur, k->vec_bytes);
   return rc;
 }
 
@@ -330,10 +349,12 @@ static int enqueue_cycle(msp_ksp *k, double *x, int K) {
   const int *stop = &k->g.st->stop;
   const double *sc = k->g.sc;
   double *sumsq = &k->g.h[0];
-  const int f32 = k->basis_prec == MSP_BASIS_F32;
-  /* f32: the initial residual waits in the current vector; VV(0) = rnd(r), the vector's norm is the rounded one's */
-  int rc = f32 ? mspi_cb_round_store(c, k->cur, k->cur, VF(k, 0), k->n, sumsq, NULL)
-               : mspi_norm2sq(c, VV(k, 0), k->n, sumsq);
+  const int f32 = k->basis_prec == MSP_BASIS_F32, b16 = k->basis_prec == MSP_BASIS_B16;
+  /* f32 / block16: the initial residual waits in the current vector; VV(0) = rnd(r), the vector's norm is the
+   * rounded one's */
+  int rc = f32   ? mspi_cb_round_store(c, k->cur, k->cur, VF(k, 0), k->n, sumsq, NULL)
+           : b16 ? mspi_cb16_round_store(c, k->cur, k->cur, VH(k, 0), EX(k, 0), k->n, sumsq, NULL)
+                 : mspi_norm2sq(c, VV(k, 0), k->n, sumsq);
   if (!rc) rc = mspi_gm_cycle_start(c, k->g, sumsq);
   int opfuse, wfree;
   step_kind(k, &opfuse, &wfree);
@@ -349,6 +370,19 @@ static int enqueue_cycle(msp_ksp *k, double *x, int K) {
   if (f32) {
     if (!rc) rc = mspi_gm_build(c, k->g, (int)k->o.restart);
     if (!rc) rc = mspi_cb_accum(c, x, &k->g.st->nbuild, VF(k, 0), k->stride, sc, k->n, k->g.grs, K);
+    return rc;
+  }
+  for (int it = 0; it < K && !rc && b16; ++it) { /* the f32 step, the basis read and written as block16 */
+    rc = mspi_spmv_scaled(k->A, k->cur, sc + it, NULL, k->tmp, stop);
+    if (!rc) rc = mspi_cb16_mdot(c, k->tmp, it + 1, VH(k, 0), k->stride, EX(k, 0), sc, k->n, k->g.h, stop);
+    if (!rc)
+      rc = mspi_cb16_maxpy_norm_update(c, k->tmp, k->cur, VH(k, it + 1), EX(k, it + 1), it + 1, VH(k, 0), k->stride,
+                                       EX(k, 0), sc, k->n, k->g, k->o.restart, stop);
+  }
+  if (b16) {
+    if (!rc) rc = mspi_gm_build(c, k->g, (int)k->o.restart);
+    if (!rc)
+      rc = mspi_cb16_accum(c, x, &k->g.st->nbuild, VH(k, 0), k->stride, EX(k, 0), sc, k->n, k->g.grs, K);
     return rc;
   }
   for (int it = 0; it < K && !rc && opfuse; ++it) {
@@ -448,9 +482,10 @@ int msp_ksp_solve(msp_ksp *k, const msp_vec *b, msp_vec *x) {
     mspi_set_error(MSP_ERR_ARG_WRONG, "b and x must be different vectors");
     return MSP_ERR_ARG_WRONG;
   }
-  if (k->basis_prec == MSP_BASIS_F32 && mspi_reduce_seq(k->ctx)) {
-    mspi_set_error(MSP_ERR_SUP, "MSP_BASIS_F32 needs the DBR reduction: MSP_REDUCE_SEQ reproduces PETSc's f64 "
-                                "sums bit for bit, which a rounded basis cannot");
+  if (compressed(k) && mspi_reduce_seq(k->ctx)) {
+    mspi_set_error(MSP_ERR_SUP, "%s needs the DBR reduction: MSP_REDUCE_SEQ reproduces PETSc's f64 "
+                                "sums bit for bit, which a rounded basis cannot",
+                   k->basis_prec == MSP_BASIS_B16 ? "MSP_BASIS_B16" : "MSP_BASIS_F32");
     return MSP_ERR_SUP;
   }
   int rc = mspi_set_device(k->ctx);
@@ -487,7 +522,7 @@ int msp_ksp_solve(msp_ksp *k, const msp_vec *b, msp_vec *x) {
   int cycle_zero_guess = guess_zero, itcount = 0, its = 0, reason = 0;
   while (!reason) {
     /* KSPInitialResidual: VV(0) = b - A x (VecCopy + VecAXPY(-1)), or b for a zero guess */
-    double *r0 = k->basis_prec == MSP_BASIS_F32 ? k->cur : VV(k, 0); /* f32: rounded into VV(0) by the cycle */
+    double *r0 = compressed(k) ? k->cur : VV(k, 0); /* f32 / block16: rounded into VV(0) by the cycle */
     if (!cycle_zero_guess) rc = mspi_residual(k->A, b->d, x->d, r0);
     else rc = mspi_copy(c, r0, b->d, k->n);
     if (rc) return rc;

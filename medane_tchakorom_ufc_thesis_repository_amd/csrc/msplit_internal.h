@@ -18,6 +18,7 @@ extern "C" {
 /* Largest number of vectors one MDot / MAXPY launch handles; more are split
  * into groups (the per-vector arithmetic does not depend on the grouping). */
 #define MSPI_MAX_GROUP 32
+#define MSPI_DBR_CHUNK 4096 /* elements per DBR chunk (MSK_DBR_CHUNK) */
 
 struct msp_vec {
   msp_ctx *ctx;
@@ -189,6 +190,20 @@ int mspi_cb_maxpy_norm_update(msp_ctx *ctx, const double *win, double *cur, floa
                               const int *stop);
 int mspi_cb_accum(msp_ctx *ctx, double *x, const int *nvdev, const float *base, int64_t stride, const double *scale,
                   int64_t n, const double *coef_dev, int nv_expected);
+/* ---- MSP_BASIS_B16: the same steps over a basis stored as int16 with one int32 exponent per DBR chunk and vector
+   (msplit_cb16.hip), VV(j) = base + j*stride, its exponents ebase + j*ceil(n/4096); all arithmetic f64, DBR only.
+   rnd16 is the rule of include/msplit.h. ---- */
+/* cur = rnd16(r) (f64; may be r itself), v0 / e0 = the same as block16, sumsq_dev[0] = sum rnd16(r)^2 */
+int mspi_cb16_round_store(msp_ctx *ctx, const double *r, double *cur, int16_t *v0, int32_t *e0, int64_t n,
+                          double *sumsq_dev, const int *stop);
+int mspi_cb16_mdot(msp_ctx *ctx, const double *w, int nv, const int16_t *base, int64_t stride, const int32_t *ebase,
+                   const double *scale, int64_t n, double *out_dev, const int *stop);
+/* s = rnd16(win - sum_j h_j VV(j)) stored to vout / eout and cur (f64), ||s||^2, then mspi_gm_norm_update */
+int mspi_cb16_maxpy_norm_update(msp_ctx *ctx, const double *win, double *cur, int16_t *vout, int32_t *eout, int nv,
+                                const int16_t *base, int64_t stride, const int32_t *ebase, const double *scale,
+                                int64_t n, mspi_gmres_dev g, int m, const int *stop);
+int mspi_cb16_accum(msp_ctx *ctx, double *x, const int *nvdev, const int16_t *base, int64_t stride,
+                    const int32_t *ebase, const double *scale, int64_t n, const double *coef_dev, int nv_expected);
 /* ---- the GMRES step's MatMult inside the CGS kernels (A in DV storage, 8-code ELL layout) ---- */
 int mspi_op_fusable(const msp_mat *A);
 /* h(0..nv-1) = (A (sdev[0] x)) . scale_j VV(j): stage 1 computes each row of A(sc x) in registers */

@@ -212,4 +212,21 @@ int msk_cb_maxpy_norm(const double* win, double* cur, float* vout, const float* 
 // x = x + (0 + sum_j coef_j VV(j)), j < *nvdev
 int msk_cb_accum(double* x, const int* nvdev, const float* vb, int64_t stride, const double* scale,
                  const double* coef, int64_t n, const int* stop, hipStream_t s);
+// ---- block-scaled basis (msplit_cb16.hip): the Krylov basis in HBM as int16 with one int32 power-of-two exponent
+// per DBR chunk and vector, VV(j) = vb + j*stride (stride a multiple of 2048), its exponents eb + j*nchunks
+// (nchunks = ceil(n / 4096)); element i of chunk c reads ldexp(q_i, eb[j*nchunks + c] - 15) * scale[j], NaN where
+// the exponent is INT32_MIN (the chunk held a NaN or an inf).  Same arithmetic and order as the msk_cb_* kernels.
+// cur = rnd16(r) as f64 (may be r itself), v0 / e0 = the same as block16, partial[c] = DBR partials of the sum
+int msk_cb16_round_store(const double* r, double* cur, int16_t* v0, int32_t* e0, int64_t n, double* partial,
+                         const int* stop, hipStream_t s);
+// DBR stage 1 of w . VV(v), v < nv <= MSK_CB_MAX_GROUP, into partial[v * nchunks + c]
+int msk_cb16_mdot(const double* w, const int16_t* vb, int64_t stride, const int32_t* eb, const double* scale, int nv,
+                  int64_t n, double* partial, int64_t nchunks, const int* stop, hipStream_t s);
+// s = rnd16(win - sum_j adev_j VV(j)) (PETSc grouping, any nv >= 1) to vout / eout and cur (f64); partials of sum s^2
+int msk_cb16_maxpy_norm(const double* win, double* cur, int16_t* vout, int32_t* eout, const int16_t* vb,
+                        int64_t stride, const int32_t* eb, const double* scale, const double* adev, int nv, int64_t n,
+                        double* partial, const int* stop, hipStream_t s);
+// x = x + (0 + sum_j coef_j VV(j)), j < *nvdev
+int msk_cb16_accum(double* x, const int* nvdev, const int16_t* vb, int64_t stride, const int32_t* eb,
+                   const double* scale, const double* coef, int64_t n, const int* stop, hipStream_t s);
 }

@@ -476,6 +476,74 @@ extern "C" int mspi_cb_accum(msp_ctx* c, double* x, const int* nvdev, const floa
   return MSP_SUCCESS;
 }
 
+// ---- MSP_BASIS_B16 (msplit_cb16.hip): the same four steps over an int16 basis with one int32 exponent per DBR
+// chunk and vector.  Byte counts: 2 per basis element plus 4 per chunk and vector, 8 per element of the f64 vectors.
+extern "C" int mspi_cb16_round_store(msp_ctx* c, const double* r, double* cur, int16_t* v0, int32_t* e0, int64_t n,
+                                     double* sumsq_dev, const int* stop) {
+  const int64_t nch = nchunks_of(n);
+  if (nch == 0) {
+    HIPCHK(hipMemsetAsync(sumsq_dev, 0, sizeof(double), c->stream));
+    return MSP_SUCCESS;
+  }
+  int rc = ensure_partial(c, nch * MSPI_MAX_GROUP);
+  if (rc) return rc;
+  KTimer kt(c, MSP_KERNEL_NORM, (8.0 + 8.0 + 2.0) * (double)n + 4.0 * (double)nch);
+  KCHK(msk_cb16_round_store(r, cur, v0, e0, n, c->partial, stop, c->stream));
+  KCHK(msk_dot_stage2(c->partial, nch, 1, sumsq_dev, stop, c->stream));
+  return MSP_SUCCESS;
+}
+
+extern "C" int mspi_cb16_mdot(msp_ctx* c, const double* w, int nv, const int16_t* base, int64_t stride,
+                              const int32_t* ebase, const double* scale, int64_t n, double* out_dev,
+                              const int* stop) {
+  if (nv <= 0) return MSP_SUCCESS;
+  const int64_t nch = nchunks_of(n);
+  if (nch == 0) {
+    HIPCHK(hipMemsetAsync(out_dev, 0, (size_t)nv * sizeof(double), c->stream));
+    return MSP_SUCCESS;
+  }
+  int rc = ensure_partial(c, nch * MSPI_MAX_GROUP);
+  if (rc) return rc;
+  const int ng = (nv + MSPI_MAX_GROUP - 1) / MSPI_MAX_GROUP;  // W is read once per launch
+  KTimer kt(c, MSP_KERNEL_MDOT, (double)n * (2.0 * nv + 8.0 * ng) + 4.0 * (double)nch * nv);
+  for (int g0 = 0; g0 < nv; g0 += MSPI_MAX_GROUP) {
+    const int g = std::min(MSPI_MAX_GROUP, nv - g0);
+    KCHK(msk_cb16_mdot(w, base + (int64_t)g0 * stride, stride, ebase + (int64_t)g0 * nch, scale + g0, g, n,
+                       c->partial, nch, stop, c->stream));
+    KCHK(msk_dot_stage2(c->partial, nch, g, out_dev + g0, stop, c->stream));
+  }
+  return MSP_SUCCESS;
+}
+
+extern "C" int mspi_cb16_maxpy_norm_update(msp_ctx* c, const double* win, double* cur, int16_t* vout, int32_t* eout,
+                                           int nv, const int16_t* base, int64_t stride, const int32_t* ebase,
+                                           const double* scale, int64_t n, mspi_gmres_dev g, int m,
+                                           const int* stop) {
+  const int64_t nch = nchunks_of(n);
+  if (nch == 0 || nv <= 0) {
+    mspi_set_error(MSP_ERR_ARG_SIZ, "maxpy_norm on an empty basis");
+    return MSP_ERR_ARG_SIZ;
+  }
+  int rc = ensure_partial(c, nch * MSPI_MAX_GROUP);
+  if (rc) return rc;
+  {
+    // W read, nv basis vectors read, VV(it+1) (2 B) and the current vector (8 B) written, the exponents
+    KTimer kt(c, MSP_KERNEL_MAXPY, (double)n * (8.0 + 2.0 * nv + 2.0 + 8.0) + 4.0 * (double)nch * (nv + 1));
+    KCHK(msk_cb16_maxpy_norm(win, cur, vout, eout, base, stride, ebase, scale, g.h, nv, n, c->partial, stop,
+                             c->stream));
+  }
+  return mspi_gm_norm_update(c, g, c->partial, nch, m);
+}
+
+extern "C" int mspi_cb16_accum(msp_ctx* c, double* x, const int* nvdev, const int16_t* base, int64_t stride,
+                               const int32_t* ebase, const double* scale, int64_t n, const double* coef_dev,
+                               int nv_expected) {
+  if (n <= 0) return MSP_SUCCESS;
+  KTimer kt(c, MSP_KERNEL_MAXPY, (double)n * (2.0 * nv_expected + 16.0) + 4.0 * (double)nchunks_of(n) * nv_expected);
+  KCHK(msk_cb16_accum(x, nvdev, base, stride, ebase, scale, coef_dev, n, nullptr, c->stream));
+  return MSP_SUCCESS;
+}
+
 
 extern "C" int mspi_scale(msp_ctx* c, double* x, int64_t n, double alpha) {
   KTimer kt(c, MSP_KERNEL_SCALE, 16.0 * (double)n);

@@ -755,8 +755,10 @@ class KSP:
         self._set(restart=int(m))
 
     # storage precision of the Krylov basis (msp_ksp_set_basis_precision): "single" keeps the basis in HBM as
-    # float with all arithmetic in double -- half the basis bytes per step and per block
-    BASIS_PRECISIONS = {"double": 0, "single": 1}
+    # float with all arithmetic in double -- half the basis bytes per step and per block; "block16" keeps it as
+    # 16-bit integers with one power-of-two exponent per 4096-entry chunk (MSP_BASIS_B16, include/msplit.h: for
+    # inexact inner solves and fixed-iteration steps) -- a quarter of the bytes
+    BASIS_PRECISIONS = {"double": 0, "single": 1, "block16": 2}
 
     def set_basis_precision(self, precision: str):
         word = str(precision).lower()

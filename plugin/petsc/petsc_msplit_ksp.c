@@ -13,16 +13,18 @@ typedef struct {
   PetscInt restart;
   PetscReal haptol, breakdowntol;
   PetscInt reduction; /* -msplit_reduction dbr|seq on this KSP's prefix; -1: the shared context's order */
-  PetscInt basis_precision; /* -msplit_basis_precision double|single: MSP_BASIS_F64 / MSP_BASIS_F32 */
+  PetscInt basis_precision; /* -msplit_basis_precision double|single|block16: MSP_BASIS_F64 / _F32 / _B16 */
 } KSP_MSplit;
 
 /* -msplit_reduction: the device reduction order (include/msplit.h msp_ctx_set_reduction).  "seq" is
  * the parity mode -- every dot, norm and MDot summed in PETSc's Seq order, so iteration counts and
  * residual histories are the reference's bit for bit -- at a fraction of the speed (bench.py seq_mode). */
 static const char *const MSplitReductions[] = {"dbr", "seq", "MSplitReduction", "MSPLIT_REDUCTION_", NULL};
-/* -msplit_basis_precision: the Krylov basis stored in HBM as double, or as float with all arithmetic in double
- * (include/msplit.h msp_ksp_set_basis_precision); single excludes -msplit_reduction seq */
-static const char *const MSplitBasisPrecisions[] = {"double", "single", "MSplitBasisPrecision", "MSPLIT_BASIS_", NULL};
+/* -msplit_basis_precision: the Krylov basis stored in HBM as double, as float, or as 16-bit integers with one
+ * power-of-two exponent per DBR chunk, all arithmetic in double (include/msplit.h msp_ksp_set_basis_precision);
+ * single and block16 exclude -msplit_reduction seq */
+static const char *const MSplitBasisPrecisions[] = {"double",  "single", "block16", "MSplitBasisPrecision",
+                                                    "MSPLIT_BASIS_", NULL};
 
 /* -msplit_minimization_precision: the operator R of msplitlsqr stored in HBM as double, or as float with all
  * arithmetic in double (include/msplit.h msp_dense_create_prec); single excludes -msplit_reduction seq */

@@ -1,0 +1,257 @@
+"""Block-scaled basis GMRES (-msplit_basis_precision block16, MSP_BASIS_B16) on the GPU.
+
+The Krylov basis is stored in HBM as 16-bit integers with one power-of-two exponent per DBR chunk and vector
+(msplit_cb16.hip) and every other number stays double, so the device solve is held to the Python twin with the
+block16 rounding (tests/basis_b16.py) bit for bit: iteration count, reason, residual norm, every history entry and
+x.  The shapes are those of tests/test_gpu_basis_f32.py, the smallest that reach each path of the four kernels: a
+partial chunk only, odd n, one full chunk plus a tail, two full chunks plus a tail, more than 32 vectors, GMRES(1),
+many restarts; every SpMV route feeds the same step; the whole double exponent range solves, a non-finite entry
+ends the solve.
+"""
+import os
+
+import numpy as np
+import pytest
+
+import basis_b16 as b16
+import basis_twin as bt
+from guarded import LEADS, Guarded, assert_same_bits, check_all
+from medane_tchakorom_ufc_thesis_repository_amd import MsplitError
+from medane_tchakorom_ufc_thesis_repository_amd.comm import LocalComm
+from medane_tchakorom_ufc_thesis_repository_amd.multisplitting import make_blocks, sm_solve
+from medane_tchakorom_ufc_thesis_repository_amd.petsc import KSP, Mat, Options, Vec
+from test_gpu_basis_f32 import BOX_CASES, _box, _box_problem, _gpu, _kw, _same, _solve_on
+from test_gpu_gmres import _opts_str, _random_csr
+
+pytestmark = pytest.mark.gpu
+
+B16 = " -msplit_basis_precision block16"
+CHUNK = 4096
+
+_twins = {}
+
+
+def _twin(name, O, b, x0, o, nonzero, rnd="block16"):
+    """A twin's solve of a named case, computed once and shared (never modified)."""
+    key = (name, rnd)
+    if key not in _twins:
+        f = {"block16": b16.block16, "f32": bt.f32}[rnd]
+        _twins[key] = bt.gmres(O, b, x0=x0, rnd=f, **_kw(o, nonzero))
+    return _twins[key]
+
+
+@pytest.mark.parametrize("name", list(BOX_CASES))
+def test_box_dv_bitwise_vs_block16_twin(ctx, oracle, name):
+    O, A, b, x0, o, nonzero = _box_problem(ctx, oracle, name)
+    A.set_storage("dv")
+    want = _twin(name, O, b, x0, o, nonzero)
+    _same(_gpu(ctx, A, b, x0, _opts_str(o, nonzero) + B16), want)
+    # the mode is really on, and it is not the float one
+    assert not np.array_equal(want[0], _twin(name, O, b, x0, o, nonzero, "f32")[0])
+
+
+@pytest.mark.parametrize("route", ["csr", "matfree", "convdiff", "random_csr"])
+def test_every_spmv_route_bitwise_vs_block16_twin(ctx, oracle, route):
+    """The step's MatMult is the operator's own scaled product on the f64 current vector, whatever the storage."""
+    nx, ny, nz = 17, 16, 16
+    o, nonzero = dict(restart=30, max_it=300, rtol=1e-4), False
+    if route == "csr":
+        O, A = _box(ctx, oracle, 3, nx, ny, nz)
+        A.set_storage("csr")
+        assert A.get_storage() == "csr"
+    elif route == "matfree":
+        O = oracle.poisson3d_rows(nx, ny, nz, 0, nz)
+        A = Mat.box_matfree(ctx, 3, nx, ny, nz)
+    elif route == "convdiff":
+        P = (0.5, -0.25, 0.125)
+        O = oracle.convdiff_rows(3, nx, ny, nz, 0, nx * ny * nz, P)
+        A = Mat.box_convdiff(ctx, 3, nx, ny, nz, False, False, P)
+    else:   # nonsymmetric, no stencil: seeded random off-diagonal pattern under a dominant diagonal
+        n = 5000
+        rp, c, v = _random_csr(np.random.default_rng(2024), n, 8)
+        O = oracle.Mat.from_arrays(n, n, rp, c, v)
+        A = Mat.from_csr(ctx, n, n, rp, c, v)
+        o = dict(restart=30, max_it=60, rtol=1e-8)
+    n = O.shape[0]
+    b = O.mult(np.ones(n)) if route != "random_csr" else np.random.default_rng(5).uniform(-1, 1, n)
+    key = "chunk_tail" if route in ("csr", "matfree") else route   # the same system as the DV case
+    _same(_gpu(ctx, A, b, None, _opts_str(o, nonzero) + B16), _twin(key, O, b, None, o, nonzero))
+
+
+@pytest.mark.parametrize("factor", [2.0 ** -140, 1e39])
+def test_whole_double_range_solves(ctx, oracle, factor):
+    """b = A 1 scaled far below and far above float range on 9x8x7: the exponent is per chunk, so both solve."""
+    O, A = _box(ctx, oracle, 3, 9, 8, 7)
+    A.set_storage("dv")
+    b = O.mult(np.ones(O.shape[0])) * factor
+    o = dict(restart=30, max_it=200, rtol=1e-10)
+    want = b16.gmres(O, b, **o)
+    assert want[1]["reason"] != bt.DIVERGED_NANORINF and want[1]["reason"] > 0 and want[1]["its"] > 0
+    _same(_gpu(ctx, A, b, None, _opts_str(o, False) + B16), want)
+
+
+def test_one_inf_in_b_diverges_nanorinf(ctx, oracle):
+    O, A = _box(ctx, oracle, 3, 9, 8, 7)
+    A.set_storage("dv")
+    b = O.mult(np.ones(O.shape[0]))
+    b[17] = np.inf
+    o = dict(restart=30, max_it=200, rtol=1e-10)
+    want = b16.gmres(O, b, **o)
+    assert (want[1]["reason"], want[1]["its"]) == (bt.DIVERGED_NANORINF, 0)
+    _same(_gpu(ctx, A, b, None, _opts_str(o, False) + B16), want)
+
+
+def test_graph_replay_equals_eager(ctx, oracle):
+    """MSPLIT_GRAPHS=0 and the default give the same bits; the second solve on one KSP replays the captured cycles."""
+    O, A, b, x0, o, nonzero = _box_problem(ctx, oracle, "chunk_tail")
+    A.set_storage("dv")
+    want = _twin("chunk_tail", O, b, x0, o, nonzero)
+
+    def twice(graphs):
+        os.environ["MSPLIT_GRAPHS"] = "1" if graphs else "0"
+        try:
+            ksp = KSP(ctx)
+            ksp.set_operators(A)
+            ksp.set_from_options(Options(_opts_str(o, nonzero) + B16))
+            bv, xv = Vec.from_array(ctx, b), Vec(ctx, A.shape[0])
+            out = []
+            for _ in range(2):
+                ksp.solve(bv, xv)
+                out.append((xv.get_array(), {"its": ksp.get_iteration_number(), "reason": ksp.get_converged_reason(),
+                                             "rnorm": ksp.get_residual_norm(), "hist": ksp.get_residual_history()}))
+            return out
+        finally:
+            os.environ.pop("MSPLIT_GRAPHS", None)
+
+    for got in twice(False) + twice(True):
+        _same(got, want)
+
+
+def test_switching_precision_on_one_ksp(ctx, oracle):
+    O, A, b, x0, o, nonzero = _box_problem(ctx, oracle, "chunk_tail")
+    w16 = _twin("chunk_tail", O, b, x0, o, nonzero)
+    w32 = _twin("chunk_tail", O, b, x0, o, nonzero, "f32")
+    w64 = oracle.gmres(O, b, x0=x0, reduce_mode=oracle.REDUCE_DBR, **_kw(o, nonzero))
+    ksp = KSP(ctx)
+    ksp.set_operators(A)
+    ksp.set_from_options(Options(_opts_str(o, nonzero)))
+    for word, want in (("double", w64), ("block16", w16), ("single", w32), ("block16", w16)):
+        ksp.set_basis_precision(word)
+        assert ksp.get_basis_precision() == word
+        _same(_solve_on(ksp, ctx, A, b, x0), want)
+
+
+def test_seq_reduction_excludes_block16(ctx, oracle):
+    O, A, b, x0, o, nonzero = _box_problem(ctx, oracle, "restart40")
+    ksp = KSP(ctx)
+    ksp.set_operators(A)
+    ksp.set_from_options(Options(_opts_str(o, nonzero) + B16))
+    before = ctx.get_reduction()
+    ctx.set_reduction("seq")
+    try:
+        with pytest.raises(MsplitError) as e:
+            _solve_on(ksp, ctx, A, b, x0)
+        assert e.value.code == 56   # PETSC_ERR_SUP
+        assert "MSP_BASIS_B16" in str(e.value)
+    finally:
+        ctx.set_reduction(before)
+    assert ctx.get_reduction() == before == "dbr"
+    _same(_solve_on(ksp, ctx, A, b, x0), _twin("restart40", O, b, x0, o, nonzero))   # and the KSP still serves
+
+
+def test_per_block_prefix_option_reaches_each_ksp(ctx):
+    nb = 2
+    opts = Options("-inner1_msplit_basis_precision block16 -inner2_msplit_basis_precision single")
+    blocks = make_blocks(ctx, 3, 12, 10, 8, nb, range(nb), opts, LocalComm())
+    assert [blk.ksp.get_basis_precision() for blk in blocks] == ["block16", "single"]
+    assert KSP.BASIS_PRECISIONS["block16"] == 2
+
+
+def test_work_bytes_block16_at_most_a_third_of_double(ctx):
+    """64^3 (a multiple of 4096), GMRES(30): 31 basis vectors.  double: 8*31 B/row (the W-free step holds no W);
+    block16: 2*31 B/row plus W and the current vector, (2*31 + 16) / (8*31) = 0.315, plus 4 B per 4096 entries of
+    exponents; the margin to 0.33 covers the recurrence block and the 4 KiB paddings."""
+    A = Mat.box_stencil(ctx, 3, 64, 64, 64)
+    n = A.shape[0]
+    assert n % CHUNK == 0
+    b = Vec.from_array(ctx, np.ones(n))
+    got = {}
+    for word in ("double", "block16"):
+        ksp = KSP(ctx)
+        ksp.set_operators(A)
+        ksp.set_from_options(Options(f"-ksp_gmres_restart 30 -ksp_max_it 40 -ksp_rtol 1e-2 "
+                                     f"-msplit_basis_precision {word}"))
+        assert ksp.get_work_bytes() == 0
+        ksp.solve(b, Vec(ctx, n))
+        got[word] = ksp.get_work_bytes()
+    print(f"work bytes at 64^3, GMRES(30): double {got['double']}, block16 {got['block16']}, "
+          f"ratio {got['block16'] / got['double']:.4f}")
+    assert got["double"] >= 8 * 31 * n
+    assert got["block16"] >= (2 * 31 + 16) * n + 4 * 31 * (n // CHUNK)
+    assert got["block16"] <= 0.33 * got["double"]
+
+
+def test_sm_driver_with_block16_inner_solves(ctx):
+    """sm_solve, 3D 12x10x8 in two blocks, the inner GMRES(30)s (max_it 20, as the campaign's) on a block16 basis:
+    the driver stops by its own f64 residual test within the max_outer the double run is given, a rerun gives the
+    same bits, and the inner solves are not the f64 ones."""
+    rtol, nb, max_outer = 1e-6, 2, 200
+
+    def run(word):
+        opts = Options(" ".join(f"-inner{k + 1}_ksp_max_it 20 -inner{k + 1}_ksp_rtol 1e-20 -inner{k + 1}_pc_type none "
+                                f"-inner{k + 1}_msplit_basis_precision {word}" for k in range(nb)))
+        comm = LocalComm()
+        blocks = make_blocks(ctx, 3, 12, 10, 8, nb, range(nb), opts, comm)
+        assert all(blk.ksp.get_basis_precision() == word for blk in blocks)
+        res = sm_solve(blocks, comm, rtol=rtol, max_outer=max_outer)
+        return res, np.concatenate([blk.x.get_array() for blk in blocks])
+
+    r1, x1 = run("block16")
+    r2, x2 = run("block16")
+    rd, xd = run("double")
+    print(f"sm_solve 12x10x8 nb=2: outer iterations block16 {r1.outer_its}, double {rd.outer_its}")
+    assert rd.outer_its < max_outer and rd.hist[-1] <= rtol * rd.norm0
+    assert r1.outer_its < max_outer and r1.hist[-1] <= rtol * r1.norm0    # stopped by the driver's f64 residual test
+    assert r1.outer_its == r2.outer_its and np.array_equal(np.array(r1.hist), np.array(r2.hist))
+    assert np.array_equal(np.array(r1.inner_its), np.array(r2.inner_its)) and np.array_equal(x1, x2)
+    assert not np.array_equal(x1, xd)
+
+
+GUARDED_CASES = {
+    "exact-chunk": dict(restart=5, max_it=12, rtol=1e-30),        # n = 4096: one full chunk, no tail
+    "chunk-plus-one": dict(restart=6, max_it=14, rtol=1e-30),     # n = 4097: a tail of one element
+    "odd-tail": dict(restart=40, max_it=45, rtol=1e-30),          # n = 4335, more than 32 vectors
+}
+
+
+@pytest.mark.parametrize("case", list(GUARDED_CASES))
+def test_gmres_block16_guarded(ctx, oracle, case):
+    """b and x in guarded windows (16-byte-only alignment, NaN guard bands) with a nonzero guess in x: the guards
+    stay intact and the result is the twin's."""
+    o = GUARDED_CASES[case]
+    if case == "chunk-plus-one":
+        n = CHUNK + 1
+        rp, col, val = _random_csr(np.random.default_rng(2024), n, 8)
+        O = oracle.Mat.from_arrays(n, n, rp, col, val)
+        A = Mat.from_csr(ctx, n, n, rp, col, val)
+    else:
+        nx, ny, nz = (16, 16, 16) if case == "exact-chunk" else (17, 17, 15)
+        O = oracle.poisson3d_rows(nx, ny, nz, 0, nz)
+        A = Mat.box_stencil(ctx, 3, nx, ny, nz)
+        n = O.shape[0]
+    assert n == {"exact-chunk": CHUNK, "chunk-plus-one": CHUNK + 1, "odd-tail": 4335}[case]
+    r = np.random.default_rng(11)
+    b, x0 = r.uniform(-1, 1, n), r.uniform(-1, 1, n)
+    want = b16.gmres(O, b, x0=x0, guess_nonzero=1, **o)
+    assert want[1]["its"] == o["max_it"]
+    for lead in LEADS:
+        B, X = Guarded.input(ctx, b, lead), Guarded.input(ctx, x0, lead)
+        ksp = KSP(ctx)
+        ksp.set_operators(A)
+        ksp.set_from_options(Options(_opts_str(o, True) + B16))
+        ksp.solve(B.vec, X.vec)
+        check_all(B, X)
+        assert_same_bits(B.get_array(), b, "b after the solve")
+        got = X.get_array(), {"its": ksp.get_iteration_number(), "reason": ksp.get_converged_reason(),
+                              "rnorm": ksp.get_residual_norm(), "hist": ksp.get_residual_history()}
+        _same(got, want)

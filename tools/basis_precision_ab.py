@@ -1,14 +1,17 @@
 """Same-process A/B of the Krylov basis precision on the flagship step (configs[1]: 3D 7-pt Poisson 256^3, GMRES(30),
-pc none, 300 iterations per solve from x0 = 0): the default f64 basis against -msplit_basis_precision single, on the
-same operator and right-hand side, interleaved A/B/A/B, for each matrix storage asked for (dv, csr).
+pc none, 300 iterations per solve from x0 = 0): the default f64 basis against -msplit_basis_precision single and
+block16, on the same operator and right-hand side, interleaved A/B/C/A/B/C, for each matrix storage asked for (dv,
+csr).
 
 Per mode one JSON line: ms_per_step (median of --rounds timed solves, host clock around a solve that ends in a device
 synchronise, after --warmup untimed solves of that mode; graphs on, timing off), the true ||b - A x|| / ||b|| after
 the step (f64 MatResidual and norms on the device), and per kernel class the TB/s of a separate solve with the
 library's per-launch events on (algorithmic bytes over event time; that solve runs eagerly, so its sum is not the
-step time).  single's line also carries ms_per_step relative to double's.
+step time) and every timed solve (ms_rounds: the spread).  Every line but double's also carries ms_per_step relative
+to double's, and block16's relative to single's.
 
-  python tools/basis_precision_ab.py [--mesh 256] [--storages dv,csr] [--rounds 7] [--warmup 2] [--out FILE]
+  python tools/basis_precision_ab.py [--mesh 256] [--storages dv,csr] [--modes double,single,block16] [--rounds 7]
+                                     [--warmup 2] [--out FILE]
 """
 from __future__ import annotations
 
@@ -21,19 +24,23 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-MODES = ("double", "single")
+ALL_MODES = ("double", "single", "block16")
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mesh", type=int, default=256)
     ap.add_argument("--storages", default="dv,csr")
+    ap.add_argument("--modes", default=",".join(ALL_MODES))
     ap.add_argument("--restart", type=int, default=30)
     ap.add_argument("--max-it", type=int, default=300)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     args = ap.parse_args()
+    MODES = tuple(args.modes.split(","))
+    if not MODES or any(m not in ALL_MODES for m in MODES):
+        raise SystemExit(f"basis_precision_ab.py: --modes takes words of {ALL_MODES}")
     import numpy as np
     import torch
     from medane_tchakorom_ufc_thesis_repository_amd.petsc import KSP, Context, Mat, Options, Vec, device_count
@@ -74,7 +81,7 @@ def main():
                 solve(mode)
         dts = {mode: [] for mode in MODES}
         for _ in range(args.rounds):
-            for mode in MODES:            # interleaved: A B A B ...
+            for mode in MODES:            # interleaved: A B C A B C ...
                 dts[mode].append(solve(mode))
         rec = {}
         for mode in MODES:
@@ -93,13 +100,16 @@ def main():
                 "tool": "basis_precision_ab", "mesh": n, "storage": A.get_storage(), "spmv_kernel": A.spmv_kernel(),
                 "restart": args.restart, "its": its, "basis_precision": mode, "ms_per_step": ms,
                 "ms_min": 1e3 * min(dts[mode]), "ms_max": 1e3 * max(dts[mode]), "rounds": args.rounds,
+                "ms_rounds": [1e3 * t for t in dts[mode]],
                 "dof_updates_per_s": rows * its / (ms * 1e-3), "true_residual_rel": true,
                 "work_bytes": ksp[mode].get_work_bytes(),
                 "kernels": {name: {"launches": s["launches"], "ms": s["ms"], "bytes_per_row_per_it": s["bytes"] / rows / its,
                                    "TB_per_s": s["bytes"] / (s["ms"] * 1e-3) / 1e12}
                             for name, s in st.items() if s["launches"] and s["ms"] > 0},
             }
-        rec["single"]["ms_per_step_vs_double"] = rec["single"]["ms_per_step"] / rec["double"]["ms_per_step"]
+        for mode, base in (("single", "double"), ("block16", "double"), ("block16", "single")):
+            if mode in rec and base in rec:
+                rec[mode][f"ms_per_step_vs_{base}"] = rec[mode]["ms_per_step"] / rec[base]["ms_per_step"]
         for mode in MODES:
             lines.append(json.dumps(rec[mode]))
             print(lines[-1], flush=True)
