@@ -185,10 +185,23 @@ typedef struct {
 
 static int ksp_from_options(msp_ksp *k, const msd_options *o, const char *p, msp_ksp_opts *ko) {
   const char *kt = msd_opt_str(o, p, "ksp_type", "gmres"), *pt = msd_opt_str(o, p, "pc_type", "none");
-  if (strcasecmp(kt, "gmres") || strcasecmp(pt, "none")) {
-    fprintf(stderr, "-%sksp_type %s -%spc_type %s: the MI355X path is gmres with pc none\n", p, kt, p, pt);
+  const int jacobi = !strcasecmp(pt, "jacobi");
+  if (strcasecmp(kt, "gmres") || (strcasecmp(pt, "none") && !jacobi)) {
+    fprintf(stderr, "-%sksp_type %s -%spc_type %s: the MI355X path is gmres with pc none or jacobi\n", p, kt, p, pt);
     return MSP_ERR_SUP;
   }
+  if (jacobi) {
+    /* left Jacobi with the preconditioned norm (KSPGMRES's defaults) is what is built; nothing else of PCJACOBI */
+    const char *side = msd_opt_str(o, p, "ksp_pc_side", "left"), *nt = msd_opt_str(o, p, "ksp_norm_type", "preconditioned");
+    const char *jt = msd_opt_str(o, p, "pc_jacobi_type", "diagonal");
+    if (strcasecmp(side, "left") || !strcasecmp(nt, "unpreconditioned") || strcasecmp(jt, "diagonal") ||
+        opt_bool(o, p, "pc_jacobi_abs", 0)) {
+      fprintf(stderr, "-%spc_type jacobi: only -%sksp_pc_side left, the preconditioned norm and -%spc_jacobi_type "
+                      "diagonal without -%spc_jacobi_abs are implemented\n", p, p, p, p);
+      return MSP_ERR_SUP;
+    }
+  }
+  CK(msp_ksp_set_pc_type(k, jacobi ? MSP_PC_JACOBI : MSP_PC_NONE));
   CK(msp_ksp_get_opts(k, ko));
   ko->restart = (int32_t)msd_opt_int(o, p, "ksp_gmres_restart", ko->restart);
   ko->max_it = (int32_t)msd_opt_int(o, p, "ksp_max_it", ko->max_it);
@@ -236,7 +249,10 @@ static int block_init(msp_ctx *ctx, const msd_problem *p, const msd_options *o, 
   B->hi = L->has_hi ? L->plane : 0;
   if (p->matfree) CK(msp_mat_create_box_matfree(ctx, L->box[0], L->box[1], L->box[2], L->box[3], 0, 0, L->peclet, &B->A));
   else CK(msp_mat_create_box_convdiff(ctx, L->box[0], L->box[1], L->box[2], L->box[3], 0, 0, L->peclet, &B->A));
-  CK(release_csr_if_dv(B->A));
+  /* initializeKSP's prefix, inner{b+1}_; Jacobi reads the operator's diagonal from its CSR, which then stays */
+  char prefix[32];
+  snprintf(prefix, sizeof(prefix), "inner%d_", b + 1);
+  if (strcasecmp(msd_opt_str(o, prefix, "pc_type", "none"), "jacobi")) CK(release_csr_if_dv(B->A));
   /* coupling rows in halo numbering: row l < plane reads halo[l] (below), row l >= n-plane reads
    * halo[lo + l - (n-plane)] (above); ascending halo index = ascending global column */
   double clo, chi;
@@ -279,8 +295,6 @@ static int block_init(msp_ctx *ctx, const msd_problem *p, const msd_options *o, 
   CK(msp_mat_mult(B->A_ext, B->xe, B->b));
   CK(msp_vec_set(B->ones, 1.0));
   /* initializeKSP (utils.c:512-541), prefix inner{b+1}_, nonzero guess */
-  char prefix[32];
-  snprintf(prefix, sizeof(prefix), "inner%d_", b + 1);
   CK(msp_ksp_create(ctx, &B->ksp));
   CK(msp_ksp_set_operators(B->ksp, B->A));
   CK(ksp_from_options(B->ksp, o, prefix, &B->ko));

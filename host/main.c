@@ -47,7 +47,8 @@ static int usage(void) {
                   "synchronous-multisplitting-synchronous-minimization-global | asynchronous-multisplitting | "
                   "asynchronous-multisplitting-asynchronous-minimization-global> "
                   "-m M -n N [-s S] [-rtol R] [-dim 3 -p P] [-peclet px,py,pz] [-nb B] [-msplit_reduction dbr|seq] [-msplit_minimization lsqr|rtr] "
-                  "[-msplit_minimization_precision double|single] [-innerK_msplit_basis_precision double|single|block16] [-json] ...\n");
+                  "[-msplit_minimization_precision double|single] [-innerK_msplit_basis_precision double|single|block16] "
+                  "[-innerK_pc_type none|jacobi] [-json] ...\n");
   return 2;
 }
 

@@ -214,6 +214,11 @@ int msp_mat_get_spmv_kernel(const msp_mat *A, const char **name);
 int msp_mat_release_csr(msp_mat *A);
 /* Download the CSR (host buffers of nrows+1 / nnz entries); synchronising. */
 int msp_mat_get_csr(const msp_mat *A, int32_t *rowptr, int32_t *col, double *val);
+/* MatGetDiagonal: d_i = a_ii as stored, 0.0 where row i stores no diagonal entry.  For every square matrix that
+ * holds its CSR arrays -- msp_mat_create_csr, the box stencil and convection-diffusion generators -- whatever
+ * storage its products read.  MSP_ERR_SUP for a row-compressed matrix (msp_mat_create_csr_rows), a matrix-free box
+ * and a matrix after msp_mat_release_csr; MSP_ERR_ARG_SIZ for a non-square matrix or a d of another size. */
+int msp_mat_get_diagonal(const msp_mat *A, msp_vec *d);
 /* MatMult y = A x (utils.c:626; KSP_PCApplyBAorAB inside KSPGMRESCycle). */
 int msp_mat_mult(msp_mat *A, const msp_vec *x, msp_vec *y);
 /* MatResidual r = b - A x (utils.c:549, :565, :579, :946;
@@ -280,7 +285,7 @@ typedef struct msp_ksp_opts {
 } msp_ksp_opts;
 
 int msp_ksp_get_default_opts(msp_ksp_opts *o);
-/* KSPCreate + KSPSetType(KSPGMRES) + PCNONE, CGS with REFINE_NEVER
+/* KSPCreate + KSPSetType(KSPGMRES) + PCNONE (msp_ksp_set_pc_type: left PCJACOBI), CGS with REFINE_NEVER
  * (initializeKSP, utils.c:512-541; canonical options running_bulk_test_g5k:64-70). */
 int msp_ksp_create(msp_ctx *ctx, msp_ksp **ksp);
 int msp_ksp_destroy(msp_ksp **ksp);
@@ -326,9 +331,31 @@ int msp_ksp_get_residual_history(const msp_ksp *ksp, const double **hist, int32_
 #define MSP_BASIS_B16 2
 int msp_ksp_set_basis_precision(msp_ksp *ksp, int prec);
 int msp_ksp_get_basis_precision(const msp_ksp *ksp, int *prec);
-/* Device bytes the KSP holds once set up and solved with: the basis, W / the current vector, and the recurrence
- * block (0 before set-up). */
+/* Device bytes the KSP holds once set up and solved with: the basis, W / the current vector, the recurrence
+ * block, and under MSP_PC_JACOBI the n doubles of the inverse diagonal (0 before set-up). */
 int msp_ksp_get_work_bytes(const msp_ksp *ksp, int64_t *bytes);
+/* Preconditioner (-pc_type none|jacobi).
+ * MSP_PC_NONE (default): PCNONE.
+ * MSP_PC_JACOBI: PETSc's PCJACOBI with -pc_jacobi_type diagonal, applied on the LEFT with the PRECONDITIONED
+ * residual norm (KSPGMRES's defaults, PC_LEFT and KSP_NORM_PRECONDITIONED):
+ *   PCSetUp  dinv_i = 1 / a_ii, one f64 division; dinv_i = 1.0 where row i stores no diagonal entry or a_ii is
+ *            +-0.0 (PETSc's "zero detected in diagonal, using 1"); a subnormal a_ii whose reciprocal overflows
+ *            gives inf and the solve ends with MSP_DIVERGED_NANORINF.  Computed at msp_ksp_set_up and again
+ *            after msp_ksp_set_operators.
+ *   PCApply  z_i = r_i * dinv_i, one f64 multiply per element (VecPointwiseMult), never a division.
+ *   The initial residual of every cycle is dinv .* (b - A x); every Arnoldi step orthogonalises
+ *   dinv .* (A v), the MatMult's result rounded first and then multiplied; with a nonzero guess and without
+ *   uirnorm the convergence test's rnorm0 is ||dinv .* b||.  The residual norm, the history and the
+ *   restart's breakdown test are all norms of the preconditioned residual; x needs no unwinding.
+ * The operator must hold its CSR arrays (msp_mat_get_diagonal's condition): MSP_ERR_SUP at set-up otherwise.
+ * Jacobi is built for the double basis and the DBR reduction only: a solve with MSP_BASIS_F32 / MSP_BASIS_B16 or
+ * on a context in MSP_REDUCE_SEQ returns MSP_ERR_SUP.  Right and symmetric preconditioning, the unpreconditioned
+ * norm and the rowmax / rowsum / rowl1 / abs variants are not implemented.  Changing the type frees the work of an
+ * earlier set-up.  Any other value: MSP_ERR_ARG_OUTOFRANGE. */
+#define MSP_PC_NONE 0
+#define MSP_PC_JACOBI 1
+int msp_ksp_set_pc_type(msp_ksp *ksp, int pc_type);
+int msp_ksp_get_pc_type(const msp_ksp *ksp, int *pc_type);
 
 /* ------------------------------------------------------------------ dense */
 /* A block of rows of a MATDENSE / MATMPIDENSE matrix, column-major in HBM with

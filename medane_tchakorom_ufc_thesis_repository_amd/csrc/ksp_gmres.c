@@ -46,6 +46,11 @@
  *            non-finite entry ends the solve.  Inside one restart cycle the recurrence residual can run ahead of
  *            the true one by about 2^-13 of the cycle's initial residual (the next restart recomputes it in f64):
  *            for inexact inner solves and fixed-iteration steps, not for gaining many digits in a single cycle.
+ *   jacobi   MSP_PC_JACOBI (msp_ksp_set_pc_type): PETSc's left Jacobi with the preconditioned norm on the f64 basis.
+ *            MatMult, MDot, MAXPY as three kernels (msplit_pcj.hip); the MatMult stores the raw W and the two CGS
+ *            kernels form dinv .* W in registers as they load it (8 more bytes per row each, no rewrite of W).  The
+ *            cycle's first kernel multiplies the initial residual by dinv in place; ||dinv .* b|| serves the
+ *            convergence test's rnorm0.  Neither opfuse nor wfree is taken; the recurrence is unchanged.
  *
  * Data layout: VV(0..min(m, max_it)) are one allocation of (min(m, max_it)+1) x stride elements; stride = n rounded
  * up to 512 doubles, to 1024 floats or to 2048 int16 (4 KiB each way); block16 keeps its int32 exponents,
@@ -88,6 +93,9 @@ struct msp_ksp {
   int64_t nchunks;          /* DBR chunks per vector */
   double *tmp;              /* device: W = A VV(it) before the orthogonalisation */
   double *cur;              /* device, F32 / B16: the newest basis vector's rounded values as doubles */
+  int pc_type;              /* MSP_PC_NONE / MSP_PC_JACOBI */
+  double *dinv;             /* device, Jacobi: n doubles, 1 / a_ii by PCSetUp's rule */
+  int dinv_valid;           /* dinv holds the current operator's (reset by msp_ksp_set_operators) */
   size_t basis_bytes, gblock_bytes, vec_bytes; /* sizes of the allocations (vec_bytes: tmp and cur, each) */
   mspi_gmres_dev g;         /* device-resident recurrence state and arrays */
   void *gblock;             /* the single device allocation behind g */
@@ -145,10 +153,12 @@ static void ksp_free_work(msp_ksp *k) {
   if (k->basis) mspi_free(k->ctx, k->basis);
   if (k->tmp) mspi_free(k->ctx, k->tmp);
   if (k->cur) mspi_free(k->ctx, k->cur);
+  if (k->dinv) mspi_free(k->ctx, k->dinv);
   if (k->gblock) mspi_free(k->ctx, k->gblock);
   if (k->hst) mspi_host_free(k->hst);
   free(k->hist);
-  k->basis = k->tmp = k->cur = NULL;
+  k->basis = k->tmp = k->cur = k->dinv = NULL;
+  k->dinv_valid = 0;
   k->expo = NULL;
   k->basis_bytes = k->gblock_bytes = k->vec_bytes = 0;
   k->gblock = NULL;
@@ -189,6 +199,7 @@ int msp_ksp_set_operators(msp_ksp *k, msp_mat *A) {
   ksp_drop_graphs(k); /* even for the same handle: a new matrix can reuse a destroyed one's address */
   k->A = A;
   k->n = nr;
+  k->dinv_valid = 0; /* PCSetUp again: the next set-up or solve recomputes the diagonal's inverse */
   return MSP_SUCCESS;
 }
 
@@ -242,13 +253,50 @@ int msp_ksp_get_basis_precision(const msp_ksp *k, int *prec) {
   return MSP_SUCCESS;
 }
 
+int msp_ksp_set_pc_type(msp_ksp *k, int pc_type) {
+  if (!k) {
+    mspi_set_error(MSP_ERR_ARG_NULL, "NULL argument");
+    return MSP_ERR_ARG_NULL;
+  }
+  if (pc_type != MSP_PC_NONE && pc_type != MSP_PC_JACOBI) {
+    mspi_set_error(MSP_ERR_ARG_OUTOFRANGE, "preconditioner %d is neither MSP_PC_NONE nor MSP_PC_JACOBI", pc_type);
+    return MSP_ERR_ARG_OUTOFRANGE;
+  }
+  if (pc_type != k->pc_type && k->setup) { /* another step and other work vectors: no graph survives */
+    msp_ctx_synchronize(k->ctx);
+    ksp_free_work(k);
+  }
+  k->pc_type = pc_type;
+  return MSP_SUCCESS;
+}
+
+int msp_ksp_get_pc_type(const msp_ksp *k, int *pc_type) {
+  if (!k || !pc_type) {
+    mspi_set_error(MSP_ERR_ARG_NULL, "NULL argument");
+    return MSP_ERR_ARG_NULL;
+  }
+  *pc_type = k->pc_type;
+  return MSP_SUCCESS;
+}
+
 int msp_ksp_get_work_bytes(const msp_ksp *k, int64_t *bytes) {
   if (!k || !bytes) {
     mspi_set_error(MSP_ERR_ARG_NULL, "NULL argument");
     return MSP_ERR_ARG_NULL;
   }
-  *bytes = (int64_t)(k->basis_bytes + k->gblock_bytes + (k->tmp ? k->vec_bytes : 0) + (k->cur ? k->vec_bytes : 0));
+  *bytes = (int64_t)(k->basis_bytes + k->gblock_bytes + (k->tmp ? k->vec_bytes : 0) + (k->cur ? k->vec_bytes : 0) +
+                    (k->dinv ? (size_t)k->n * sizeof(double) : 0));
   return MSP_SUCCESS;
+}
+
+/* PCSetUp of MSP_PC_JACOBI: dinv allocated with the work, computed once per operator */
+static int pc_set_up(msp_ksp *k) {
+  if (k->pc_type != MSP_PC_JACOBI || k->dinv_valid) return MSP_SUCCESS;
+  int rc = MSP_SUCCESS;
+  if (!k->dinv) rc = mspi_malloc(k->ctx, (void **)&k->dinv, (size_t)(k->n ? k->n : 1) * sizeof(double));
+  if (!rc) rc = mspi_pcj_diag_inv(k->A, k->dinv);
+  if (!rc) k->dinv_valid = 1;
+  return rc;
 }
 
 int msp_ksp_set_up(msp_ksp *k) {
@@ -256,7 +304,7 @@ int msp_ksp_set_up(msp_ksp *k) {
     mspi_set_error(MSP_ERR_ARG_WRONG, "KSPSetUp before KSPSetOperators");
     return MSP_ERR_ARG_WRONG;
   }
-  if (k->setup) return MSP_SUCCESS;
+  if (k->setup) return pc_set_up(k);
   const int64_t m = k->o.restart;
   /* a cycle runs K <= min(restart, max_it) steps and touches VV(0..K): with max_it < restart (the campaign's
    * inner solves, max_it 20 under GMRES(30)) only max_it + 1 basis vectors are ever used -- 11 of 32 GB less
@@ -308,7 +356,8 @@ int msp_ksp_set_up(msp_ksp *k) {
   d += m + 2;
   k->g.hist = d;
   k->setup = 1;
-  return MSP_SUCCESS;
+  if ((rc = pc_set_up(k))) ksp_free_work(k);
+  return rc;
 }
 
 static double *VV(const msp_ksp *k, int j) { return k->basis + (int64_t)j * k->stride; }
@@ -322,6 +371,10 @@ static int compressed(const msp_ksp *k) { return k->basis_prec != MSP_BASIS_F64;
  * operator and msk_set_gm_wfree, so it is asked again before every solve. */
 static void step_kind(const msp_ksp *k, int *opfuse, int *wfree) {
   if (compressed(k)) { /* those kernels read an f64 basis: the f32 / block16 step stores W */
+    *opfuse = *wfree = 0;
+    return;
+  }
+  if (k->pc_type == MSP_PC_JACOBI) { /* w = dinv .* W is formed by the CGS kernels from the stored W */
     *opfuse = *wfree = 0;
     return;
   }
@@ -350,6 +403,23 @@ static int enqueue_cycle(msp_ksp *k, double *x, int K) {
   const double *sc = k->g.sc;
   double *sumsq = &k->g.h[0];
   const int f32 = k->basis_prec == MSP_BASIS_F32, b16 = k->basis_prec == MSP_BASIS_B16;
+  if (k->pc_type == MSP_PC_JACOBI) {
+    /* left Jacobi on the f64 basis: VV(0) = dinv .* r in place and its norm; per step the raw W = A (sc[it] VV(it))
+     * is stored, h = (dinv .* W) . sc.VV(0..it), VV(it+1) = dinv .* W - sum h_j sc[j] VV(j) and its norm -- both
+     * kernels form dinv .* W as they load W.  The recurrence and BuildSoln are the unpreconditioned ones. */
+    int rc = mspi_pcj_apply_norm(c, VV(k, 0), k->dinv, VV(k, 0), k->n, sumsq, NULL);
+    if (!rc) rc = mspi_gm_cycle_start(c, k->g, sumsq);
+    for (int it = 0; it < K && !rc; ++it) {
+      rc = mspi_spmv_scaled(k->A, VV(k, it), sc + it, NULL, k->tmp, stop);
+      if (!rc) rc = mspi_pcj_mdot(c, k->tmp, k->dinv, it + 1, k->basis, k->stride, sc, k->n, k->g.h, stop);
+      if (!rc)
+        rc = mspi_pcj_maxpy_norm_update(c, k->tmp, k->dinv, VV(k, it + 1), it + 1, k->basis, k->stride, sc, k->n,
+                                        k->g, k->o.restart, stop);
+    }
+    if (!rc) rc = mspi_gm_build(c, k->g, (int)k->o.restart);
+    if (!rc) rc = mspi_maxpy_accum_basis(c, x, &k->g.st->nbuild, k->basis, k->stride, sc, k->n, k->g.grs, K);
+    return rc;
+  }
   /* f32 / block16: the initial residual waits in the current vector; VV(0) = rnd(r), the vector's norm is the
    * rounded one's */
   int rc = f32   ? mspi_cb_round_store(c, k->cur, k->cur, VF(k, 0), k->n, sumsq, NULL)
@@ -488,6 +558,15 @@ int msp_ksp_solve(msp_ksp *k, const msp_vec *b, msp_vec *x) {
                    k->basis_prec == MSP_BASIS_B16 ? "MSP_BASIS_B16" : "MSP_BASIS_F32");
     return MSP_ERR_SUP;
   }
+  if (k->pc_type == MSP_PC_JACOBI && compressed(k)) {
+    mspi_set_error(MSP_ERR_SUP, "MSP_PC_JACOBI is built for the double basis only, not %s",
+                   k->basis_prec == MSP_BASIS_B16 ? "MSP_BASIS_B16" : "MSP_BASIS_F32");
+    return MSP_ERR_SUP;
+  }
+  if (k->pc_type == MSP_PC_JACOBI && mspi_reduce_seq(k->ctx)) {
+    mspi_set_error(MSP_ERR_SUP, "MSP_PC_JACOBI needs the DBR reduction: its fused kernels have no MSP_REDUCE_SEQ form");
+    return MSP_ERR_SUP;
+  }
   int rc = mspi_set_device(k->ctx);
   if (!rc) rc = msp_ksp_set_up(k);
   if (!rc) rc = ensure_w(k);
@@ -512,7 +591,10 @@ int msp_ksp_solve(msp_ksp *k, const msp_vec *b, msp_vec *x) {
   h->scale = 1.0;
   if (!guess_zero && !k->o.uirnorm) { /* KSPConvergedDefault at n == 0 needs ||b|| */
     double bb = 0.0;
-    if ((rc = mspi_norm2sq(c, b->d, k->n, k->g.h))) return rc;
+    /* under Jacobi ||dinv .* b||, the product written to W (free until the first MatMult) */
+    if (k->pc_type == MSP_PC_JACOBI) rc = mspi_pcj_apply_norm(c, b->d, k->dinv, k->tmp, k->n, k->g.h, NULL);
+    else rc = mspi_norm2sq(c, b->d, k->n, k->g.h);
+    if (rc) return rc;
     if ((rc = mspi_d2h_sync(c, &bb, k->g.h, sizeof(double)))) return rc;
     h->bnorm = sqrt(bb);
   }

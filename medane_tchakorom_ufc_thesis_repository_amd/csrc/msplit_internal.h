@@ -204,6 +204,23 @@ int mspi_cb16_maxpy_norm_update(msp_ctx *ctx, const double *win, double *cur, in
                                 int64_t n, mspi_gmres_dev g, int m, const int *stop);
 int mspi_cb16_accum(msp_ctx *ctx, double *x, const int *nvdev, const int16_t *base, int64_t stride,
                     const int32_t *ebase, const double *scale, int64_t n, const double *coef_dev, int nv_expected);
+/* ---- MSP_PC_JACOBI: left Jacobi preconditioning fused into the CGS kernels over the f64 basis (msplit_pcj.hip);
+   dinv = n doubles from mspi_pcj_diag_inv, w = W .* dinv formed as W is loaded (W stays as the MatMult wrote it),
+   everything after that multiply the f64 step's arithmetic; DBR only. ---- */
+/* d_i = a_ii (0.0 where row i stores none); MSP_ERR_SUP unless A holds its CSR arrays (not row-compressed, not
+   matrix-free, not released), MSP_ERR_ARG_SIZ unless A is square */
+int mspi_mat_diagonal(const msp_mat *A, double *d);
+/* PCSetUp: dinv_i = 1 / a_ii, 1.0 where a_ii is +-0.0 or absent; the same refusals */
+int mspi_pcj_diag_inv(const msp_mat *A, double *dinv);
+/* z = r .* dinv (z may be r itself), sumsq_dev[0] = sum z^2 */
+int mspi_pcj_apply_norm(msp_ctx *ctx, const double *r, const double *dinv, double *z, int64_t n, double *sumsq_dev,
+                        const int *stop);
+int mspi_pcj_mdot(msp_ctx *ctx, const double *w, const double *dinv, int nv, const double *base, int64_t stride,
+                  const double *scale, int64_t n, double *out_dev, const int *stop);
+/* vout = (win .* dinv) - sum_j h_j VV(j), ||vout||^2, then mspi_gm_norm_update */
+int mspi_pcj_maxpy_norm_update(msp_ctx *ctx, const double *win, const double *dinv, double *vout, int nv,
+                               const double *base, int64_t stride, const double *scale, int64_t n, mspi_gmres_dev g,
+                               int m, const int *stop);
 /* ---- the GMRES step's MatMult inside the CGS kernels (A in DV storage, 8-code ELL layout) ---- */
 int mspi_op_fusable(const msp_mat *A);
 /* h(0..nv-1) = (A (sdev[0] x)) . scale_j VV(j): stage 1 computes each row of A(sc x) in registers */

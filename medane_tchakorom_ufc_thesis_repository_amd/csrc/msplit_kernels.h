@@ -229,4 +229,19 @@ int msk_cb16_maxpy_norm(const double* win, double* cur, int16_t* vout, int32_t* 
 // x = x + (0 + sum_j coef_j VV(j)), j < *nvdev
 int msk_cb16_accum(double* x, const int* nvdev, const int16_t* vb, int64_t stride, const int32_t* eb,
                    const double* scale, const double* coef, int64_t n, const int* stop, hipStream_t s);
+// ---- left Jacobi preconditioning of GMRES (msplit_pcj.hip): the f64 basis, VV(j) = vb + j*stride, its value
+// VV(j)[i] * scale[j]; w = W .* dinv formed in registers; DBR lane map and order, the f64 step's arithmetic.
+// out_i = a_ii of the CSR (0.0 where row i stores none); invert: 1 / a_ii, and 1.0 where a_ii is +-0.0 or absent
+int msk_pcj_diag(const int32_t* rowptr, const int32_t* col, const double* val, int32_t n, double* out, int invert,
+                 hipStream_t s);
+// z = r .* dinv (z may be r itself), partial[c] = DBR partials of sum z^2
+int msk_pcj_apply_norm(const double* r, const double* dinv, double* z, int64_t n, double* partial, const int* stop,
+                       hipStream_t s);
+// DBR stage 1 of (w .* dinv) . VV(v), v < nv <= MSK_CB_MAX_GROUP, into partial[v * nchunks + c]
+int msk_pcj_mdot(const double* w, const double* dinv, const double* vb, int64_t stride, const double* scale, int nv,
+                 int64_t n, double* partial, int64_t nchunks, const int* stop, hipStream_t s);
+// vout = (win .* dinv) - sum_j adev_j VV(j) (PETSc grouping, any nv >= 1); partials of its sum of squares
+int msk_pcj_maxpy_norm(const double* win, const double* dinv, double* vout, const double* vb, int64_t stride,
+                       const double* scale, const double* adev, int nv, int64_t n, double* partial, const int* stop,
+                       hipStream_t s);
 }

@@ -544,6 +544,63 @@ extern "C" int mspi_cb16_accum(msp_ctx* c, double* x, const int* nvdev, const in
   return MSP_SUCCESS;
 }
 
+// ---- MSP_PC_JACOBI (msplit_pcj.hip): the stored-W step over the f64 basis with w = W .* dinv formed in the CGS
+// kernels.  Byte counts: the f64 kernels' plus 8 per row for dinv.  The MSPLIT_TUNING variants of the f64 MDot /
+// MAXPY do not apply: each step has one kernel.
+extern "C" int mspi_pcj_apply_norm(msp_ctx* c, const double* r, const double* dinv, double* z, int64_t n,
+                                   double* sumsq_dev, const int* stop) {
+  const int64_t nch = nchunks_of(n);
+  if (nch == 0) {
+    HIPCHK(hipMemsetAsync(sumsq_dev, 0, sizeof(double), c->stream));
+    return MSP_SUCCESS;
+  }
+  int rc = ensure_partial(c, nch * MSPI_MAX_GROUP);
+  if (rc) return rc;
+  KTimer kt(c, MSP_KERNEL_NORM, 24.0 * (double)n);  // r and dinv read, z written
+  KCHK(msk_pcj_apply_norm(r, dinv, z, n, c->partial, stop, c->stream));
+  KCHK(msk_dot_stage2(c->partial, nch, 1, sumsq_dev, stop, c->stream));
+  return MSP_SUCCESS;
+}
+
+extern "C" int mspi_pcj_mdot(msp_ctx* c, const double* w, const double* dinv, int nv, const double* base,
+                             int64_t stride, const double* scale, int64_t n, double* out_dev, const int* stop) {
+  if (nv <= 0) return MSP_SUCCESS;
+  const int64_t nch = nchunks_of(n);
+  if (nch == 0) {
+    HIPCHK(hipMemsetAsync(out_dev, 0, (size_t)nv * sizeof(double), c->stream));
+    return MSP_SUCCESS;
+  }
+  int rc = ensure_partial(c, nch * MSPI_MAX_GROUP);
+  if (rc) return rc;
+  const int ng = (nv + MSPI_MAX_GROUP - 1) / MSPI_MAX_GROUP;  // W and dinv are read once per launch
+  KTimer kt(c, MSP_KERNEL_MDOT, (double)n * (8.0 * nv + 16.0 * ng));
+  for (int g0 = 0; g0 < nv; g0 += MSPI_MAX_GROUP) {
+    const int g = std::min(MSPI_MAX_GROUP, nv - g0);
+    KCHK(msk_pcj_mdot(w, dinv, base + (int64_t)g0 * stride, stride, scale + g0, g, n, c->partial, nch, stop,
+                      c->stream));
+    KCHK(msk_dot_stage2(c->partial, nch, g, out_dev + g0, stop, c->stream));
+  }
+  return MSP_SUCCESS;
+}
+
+extern "C" int mspi_pcj_maxpy_norm_update(msp_ctx* c, const double* win, const double* dinv, double* vout, int nv,
+                                          const double* base, int64_t stride, const double* scale, int64_t n,
+                                          mspi_gmres_dev g, int m, const int* stop) {
+  const int64_t nch = nchunks_of(n);
+  if (nch == 0 || nv <= 0) {
+    mspi_set_error(MSP_ERR_ARG_SIZ, "maxpy_norm on an empty basis");
+    return MSP_ERR_ARG_SIZ;
+  }
+  int rc = ensure_partial(c, nch * MSPI_MAX_GROUP);
+  if (rc) return rc;
+  {
+    // W and dinv read, nv basis vectors read, VV(it+1) written
+    KTimer kt(c, MSP_KERNEL_MAXPY, (double)n * (16.0 + 8.0 * nv + 8.0));
+    KCHK(msk_pcj_maxpy_norm(win, dinv, vout, base, stride, scale, g.h, nv, n, c->partial, stop, c->stream));
+  }
+  return mspi_gm_norm_update(c, g, c->partial, nch, m);
+}
+
 
 extern "C" int mspi_scale(msp_ctx* c, double* x, int64_t n, double alpha) {
   KTimer kt(c, MSP_KERNEL_SCALE, 16.0 * (double)n);
@@ -1264,6 +1321,21 @@ extern "C" int msp_mat_get_csr(const msp_mat* A, int32_t* rowptr, int32_t* col, 
   return MSP_SUCCESS;
 }
 
+// MatGetDiagonal and the Jacobi set-up read the resident CSR, whatever storage the products read
+static int diag_impl(const msp_mat* A, double* out, int invert) {
+  ARGCHK(A && out, MSP_ERR_ARG_NULL, "NULL argument");
+  ARGCHK(!A->matfree, MSP_ERR_SUP, "no stored diagonal (matrix-free operator)");
+  ARGCHK(!A->compressed, MSP_ERR_SUP, "the diagonal of a row-compressed matrix is not available");
+  ARGCHK(!A->csr_released && A->rowptr && (A->nnz == 0 || (A->col && A->val)), MSP_ERR_SUP,
+         "CSR storage released (msp_mat_release_csr)");
+  ARGCHK(A->nrows == A->ncols, MSP_ERR_ARG_SIZ, "the diagonal needs a square matrix, got %d x %d", A->nrows,
+         A->ncols);
+  KCHK(msk_pcj_diag(A->rowptr, A->col, A->val, A->nrows, out, invert, A->ctx->stream));
+  return MSP_SUCCESS;
+}
+extern "C" int mspi_mat_diagonal(const msp_mat* A, double* d) { return diag_impl(A, d, 0); }
+extern "C" int mspi_pcj_diag_inv(const msp_mat* A, double* dinv) { return diag_impl(A, dinv, 1); }
+
 static double spmv_bytes(const msp_mat* A, bool resid) {
   const double rows = A->compressed ? (double)A->nlisted : (double)A->nrows;
   const double xs = A->compressed ? (double)A->nnz : (double)A->ncols;
@@ -1728,6 +1800,15 @@ extern "C" int msp_mat_mult(msp_mat* A, const msp_vec* x, msp_vec* y) {
          "MatMult sizes: A %d x %d, x %lld, y %lld", A->nrows, A->ncols, (long long)x->n, (long long)y->n);
   ARGCHK(x->d != y->d, MSP_ERR_ARG_WRONG, "x and y must be different vectors");
   return mspi_spmv(A, x->d, y->d);
+}
+
+extern "C" int msp_mat_get_diagonal(const msp_mat* A, msp_vec* d) {
+  ARGCHK(A, MSP_ERR_ARG_NULL, "mat is NULL");
+  int rc;
+  if ((rc = vec_ok(d, "d"))) return rc;
+  ARGCHK(A->nrows != A->ncols || d->n == A->nrows, MSP_ERR_ARG_SIZ, "MatGetDiagonal sizes: A %d x %d, d %lld",
+         A->nrows, A->ncols, (long long)d->n);
+  return mspi_mat_diagonal(A, d->d);
 }
 
 extern "C" int msp_mat_residual(msp_mat* A, const msp_vec* b, const msp_vec* x, msp_vec* r) {

@@ -46,7 +46,10 @@ class GpuBlock:
             self.A = Mat.box_convdiff(ctx, dim, bx, by, bz, False, False, self.peclet)
         # DV storage holds the operator in ~1 byte per entry; its CSR copy is freed unless -msplit_keep_csr
         self._release_csr = not (opts is not None and opts.get_bool("msplit_keep_csr", False))
-        self._maybe_release_csr(self.A)
+        self.prefix = prefix if prefix is not None else f"inner{layout.b + 1}_"
+        # -<prefix>pc_type jacobi reads the operator's diagonal from its CSR, which then stays
+        if not (opts is not None and str(opts.get_string("pc_type", "none", self.prefix)).lower() == "jacobi"):
+            self._maybe_release_csr(self.A)
         row_ids, rowptr, col, val = layout.coupling
         self.A_off = Mat.from_csr_rows(ctx, n, layout.halo_size, row_ids, rowptr, col, val)
         self.halo, self.halo_t = comm.alloc(ctx, layout.halo_size)
@@ -66,7 +69,6 @@ class GpuBlock:
         ones.set(1.0)
         self.A_ext.mult(ones, self.b)
         del ones
-        self.prefix = prefix if prefix is not None else f"inner{layout.b + 1}_"
         self.opts = opts
         self.ksp = initializeKSP(ctx, self.A, False, self.prefix, opts)
         self.last_its = 0

@@ -340,6 +340,13 @@ class Mat:
         call("msp_mat_get_csr", self.h, _ip(rp), _ip(cl), _dp(vl))
         return rp, cl[: self.nnz], vl[: self.nnz]
 
+    def get_diagonal(self, d: Vec | None = None) -> Vec:            # MatGetDiagonal
+        """d_i = a_ii as stored, 0.0 where row i stores none (msp_mat_get_diagonal), into d or a new Vec;
+        PETSC_ERR_SUP for a row-compressed or matrix-free matrix and after release_csr."""
+        d = Vec(self.ctx, self.shape[0]) if d is None else d
+        call("msp_mat_get_diagonal", self.h, d.h)
+        return d
+
     STORAGE = {"none": -1, "csr": 0, "dv": 1, "stencil": 2}
 
     def set_storage(self, storage: str):
@@ -703,7 +710,7 @@ class LSQR:
 
 # ------------------------------------------------------------------------- KSP
 class KSP:
-    """KSPGMRES with PCNONE (the reference's canonical inner solver,
+    """KSPGMRES with PCNONE or left PCJACOBI (PCNONE: the reference's canonical inner solver,
     running_bulk_test_g5k:64-70; initializeKSP, utils.c:512-541)."""
 
     def __init__(self, ctx: Context):
@@ -772,8 +779,41 @@ class KSP:
         call("msp_ksp_get_basis_precision", self.h, C.byref(v))
         return {n: w for w, n in self.BASIS_PRECISIONS.items()}[v.value]
 
+    # preconditioner (msp_ksp_set_pc_type): "jacobi" is PETSc's PCJACOBI (diagonal) on the left with the
+    # preconditioned residual norm, KSPGMRES's defaults; double basis and DBR reduction only
+    PC_TYPES = {"none": 0, "jacobi": 1}
+
+    def set_pc_type(self, pc_type: str):                            # PCSetType
+        word = str(pc_type).lower()
+        if word not in self.PC_TYPES:
+            raise MsplitError(PETSC_ERR_SUP, f"pc type {pc_type!r}: expected one of {sorted(self.PC_TYPES)}")
+        call("msp_ksp_set_pc_type", self.h, self.PC_TYPES[word])
+
+    def get_pc_type(self) -> str:                                   # PCGetType
+        v = C.c_int()
+        call("msp_ksp_get_pc_type", self.h, C.byref(v))
+        return {n: w for w, n in self.PC_TYPES.items()}[v.value]
+
+    @staticmethod
+    def _check_jacobi_options(opts: Options, p: str):
+        """What -pc_type jacobi is not built with: each is PETSC_ERR_SUP naming the option."""
+        side = opts.get_string("ksp_pc_side", "left", p).lower()
+        if side != "left":
+            raise MsplitError(PETSC_ERR_SUP, f"-{p}ksp_pc_side {side} with -{p}pc_type jacobi: only left "
+                                             "preconditioning is implemented")
+        nt = opts.get_string("ksp_norm_type", "preconditioned", p).lower()
+        if nt == "unpreconditioned":
+            raise MsplitError(PETSC_ERR_SUP, f"-{p}ksp_norm_type unpreconditioned with -{p}pc_type jacobi: PETSc "
+                                             "switches to right preconditioning there, which is not implemented")
+        jt = opts.get_string("pc_jacobi_type", "diagonal", p).lower()
+        if jt != "diagonal":
+            raise MsplitError(PETSC_ERR_SUP, f"-{p}pc_jacobi_type {jt}: only diagonal is implemented")
+        if opts.get_bool("pc_jacobi_abs", False, p):
+            raise MsplitError(PETSC_ERR_SUP, f"-{p}pc_jacobi_abs is not implemented")
+
     def get_work_bytes(self) -> int:
-        """Device bytes held after set-up and the first solve: basis, W / current vector, recurrence block."""
+        """Device bytes held after set-up and the first solve: basis, W / current vector, recurrence block, and
+        under Jacobi the inverse diagonal."""
         v = C.c_int64()
         call("msp_ksp_get_work_bytes", self.h, C.byref(v))
         return v.value
@@ -783,9 +823,12 @@ class KSP:
         kt = opts.get_string("ksp_type", "gmres", p)
         if kt.lower() != "gmres":
             raise MsplitError(PETSC_ERR_SUP, f"-{p}ksp_type {kt}: only gmres is implemented on the MI355X path")
-        pt = opts.get_string("pc_type", "none", p)
-        if pt.lower() != "none":
-            raise MsplitError(PETSC_ERR_SUP, f"-{p}pc_type {pt}: only none is implemented on the MI355X path")
+        pt = opts.get_string("pc_type", self.get_pc_type(), p)
+        if pt.lower() not in self.PC_TYPES:
+            raise MsplitError(PETSC_ERR_SUP, f"-{p}pc_type {pt}: only none and jacobi are implemented on the "
+                                             "MI355X path")
+        if pt.lower() == "jacobi":
+            self._check_jacobi_options(opts, p)
         if opts.has("ksp_gmres_modifiedgramschmidt", p):
             raise MsplitError(PETSC_ERR_SUP, "modified Gram-Schmidt is not implemented (CGS only)")
         rt = opts.get_string("ksp_gmres_cgs_refinement_type", "refine_never", p)
@@ -813,6 +856,8 @@ class KSP:
                 raise MsplitError(PETSC_ERR_ARG_OUTOFRANGE, f"-{p}msplit_basis_precision {word}: expected one of "
                                                             f"{sorted(self.BASIS_PRECISIONS)}")
             self.set_basis_precision(word)
+        if opts.has("pc_type", p):
+            self.set_pc_type(pt)
 
     def set_up(self):
         call("msp_ksp_set_up", self.h)

@@ -1,0 +1,469 @@
+"""Left Jacobi preconditioning of GMRES (-pc_type jacobi, MSP_PC_JACOBI) on the GPU.
+
+PETSc's PCJACOBI (diagonal) on the left with the preconditioned norm, fused into the CGS kernels
+(msplit_pcj.hip).  Every solve is held to the Python twin (tests/pc_twin.py, itself pinned to the C oracle by
+tests/test_pc_twin.py) bit for bit: iteration count, reason, residual norm, every history entry and x.  The
+operators have a variable diagonal and reach every MatMult route; the shapes are the smallest that reach each path
+of the kernels: a partial chunk only, odd n, one chunk plus a tail, two chunks plus a tail, more than 32 vectors,
+GMRES(1), many restarts, max_it below the restart.
+"""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+
+import pc_twin as pt
+from guarded import Guarded, check_all
+from medane_tchakorom_ufc_thesis_repository_amd import MsplitError, _lib
+from medane_tchakorom_ufc_thesis_repository_amd.comm import LocalComm
+from medane_tchakorom_ufc_thesis_repository_amd.multisplitting import make_blocks, sm_solve
+from medane_tchakorom_ufc_thesis_repository_amd.petsc import KSP, Mat, Options, Vec
+from medane_tchakorom_ufc_thesis_repository_amd.utils import heterogeneous_poisson3d
+from test_pc_twin import IDENTITY_OPTS, poisson2d_identity_problem
+
+pytestmark = pytest.mark.gpu
+
+ERR_SUP, ERR_ARG_OUTOFRANGE, ERR_ARG_SIZ = 56, 63, 60
+DIVERGED_NANORINF = -9
+
+
+def _opts_str(o, pc="jacobi"):
+    s = (f"-ksp_type gmres -pc_type {pc} -ksp_gmres_restart {o['restart']} -ksp_max_it {o['max_it']} "
+         f"-ksp_rtol {o['rtol']}")
+    if o.get("uirnorm"):
+        s += " -ksp_converged_use_initial_residual_norm"
+    if o.get("guess_nonzero"):
+        s += " -ksp_initial_guess_nonzero"
+    return s
+
+
+def _result(ksp, xv):
+    return xv.get_array(), {"its": ksp.get_iteration_number(), "reason": ksp.get_converged_reason(),
+                            "rnorm": ksp.get_residual_norm(), "hist": ksp.get_residual_history()}
+
+
+def _solve_on(ksp, ctx, A, b, x0):
+    bv = Vec.from_array(ctx, b)
+    xv = Vec.from_array(ctx, x0) if x0 is not None else Vec(ctx, A.shape[0])
+    ksp.solve(bv, xv)
+    return _result(ksp, xv)
+
+
+def _gpu(ctx, A, b, x0, optstr):
+    ksp = KSP(ctx)
+    ksp.set_operators(A)
+    ksp.set_from_options(Options(optstr))
+    return _solve_on(ksp, ctx, A, b, x0)
+
+
+def _same(got, want):
+    (xg, rg), (xw, rw) = got, want
+    assert (rg["its"], rg["reason"]) == (rw["its"], rw["reason"])
+    assert rg["rnorm"] == rw["rnorm"] or (np.isnan(rg["rnorm"]) and np.isnan(rw["rnorm"]))
+    assert np.array_equal(rg["hist"], rw["hist"], equal_nan=True)
+    assert np.array_equal(xg, xw, equal_nan=True)
+
+
+def _random_csr(rng, n, max_row):
+    """Nonsymmetric, diagonally dominant, ragged rows (0..max_row off-diagonals), sorted columns (the recipe of
+    tests/test_gpu_gmres.py)."""
+    rows, cols, vals = [], [], []
+    for r in range(n):
+        k = int(rng.integers(0, max_row + 1))
+        c = np.unique(np.concatenate([[r], rng.integers(0, n, k)]))
+        v = rng.uniform(-1, 1, c.size)
+        v[c == r] = 1.0 + np.abs(v).sum()
+        rows.append(np.full(c.size, r))
+        cols.append(c)
+        vals.append(v)
+    cols, vals = np.concatenate(cols), np.concatenate(vals)
+    rp = np.concatenate([[0], np.cumsum([x.size for x in rows])])
+    return rp.astype(np.int32), cols.astype(np.int32), vals
+
+
+def _variable_diagonal_csr(n=5000):
+    """The seeded random CSR with its diagonal multiplied by a seeded factor in [1, 100]."""
+    rp, col, val = _random_csr(np.random.default_rng(2024), n, 8)
+    rows = np.repeat(np.arange(n), np.diff(rp))
+    val = val.copy()
+    val[col == rows] *= np.random.default_rng(31).uniform(1.0, 100.0, n)
+    return rp, col, val
+
+
+def _unsymmetric(rp, col, val):
+    """A few upper entries scaled (the recipe of tests/test_gpu_dv.py): the stencil storage keeps seven legs."""
+    val = val.copy()
+    rows = np.repeat(np.arange(rp.size - 1), np.diff(rp))
+    upper = np.flatnonzero(col > rows)
+    pick = np.random.default_rng(20240229).choice(upper, size=max(1, upper.size // 1000), replace=False)
+    val[pick] *= 1.5
+    return val
+
+
+_cache = {}
+
+
+def _problem(oracle, name):
+    """(rowptr, col, val, O, b, dinv) of a named operator, built once and shared (never modified)."""
+    if name in _cache:
+        return _cache[name]
+    if name == "random_csr":
+        rp, col, val = _variable_diagonal_csr()
+    elif name == "convdiff":
+        rp, col, val = oracle.convdiff_rows(3, 17, 16, 16, 0, 17 * 16 * 16, (0.5, -0.25, 0.125)).arrays()
+    else:                                            # "box-<nx>x<ny>x<nz>[-unsym]": per-row values
+        shape = tuple(int(s) for s in name.split("-")[1].split("x"))
+        rp, col, val = heterogeneous_poisson3d(*shape)
+        if name.endswith("-unsym"):
+            val = _unsymmetric(rp, col, val)
+    n = len(rp) - 1
+    O = oracle.Mat.from_arrays(n, n, rp, col, val)
+    b = np.random.default_rng(5).uniform(-1, 1, n)
+    _cache[name] = (rp, col, val, O, b, pt.jacobi_dinv(rp, col, val))
+    return _cache[name]
+
+
+_twins = {}
+
+
+def _twin(oracle, name, o, x0=None):
+    key = (name, tuple(sorted(o.items())), x0 is not None)
+    if key not in _twins:
+        _, _, _, O, b, dinv = _problem(oracle, name)
+        _twins[key] = pt.gmres(O, b, dinv, x0=x0, **o)
+    return _twins[key]
+
+
+def _x0(n):
+    return np.random.default_rng(7).uniform(-1, 1, n)
+
+
+ROUTE_OPTS = dict(restart=30, max_it=60, rtol=1e-8)
+
+
+# ------------------------------------------------------------------ variable diagonals through every MatMult route
+@pytest.mark.parametrize("name,storage", [
+    ("random_csr", "csr"),
+    ("box-17x16x16", None), ("box-17x16x16-unsym", None),          # n = 4352: one chunk plus a tail
+    ("box-64x64x2", "stencil"), ("box-64x64x2-unsym", "stencil"),   # planes of whole chunks: both STENCIL layouts
+    ("box-64x64x2", "csr"), ("box-64x64x2-unsym", "csr"),           # the same matrices forced to CSR
+    ("convdiff", None),
+])
+def test_variable_diagonal_bitwise_vs_twin(ctx, oracle, name, storage):
+    rp, col, val, O, b, dinv = _problem(oracle, name)
+    n = O.shape[0]
+    assert np.unique(dinv).size > 1 or name == "convdiff"
+    if name == "convdiff":
+        A = Mat.box_convdiff(ctx, 3, 17, 16, 16, False, False, (0.5, -0.25, 0.125))
+    else:
+        A = Mat.from_csr(ctx, n, n, rp, col, val)
+    if name.startswith("box-64") and storage == "stencil":
+        assert A.get_storage() == "stencil"                                      # the library's own pick
+        assert A.spmv_kernel() == ("k_box_march_chunk_rv" if name.endswith("unsym") else "k_box_march_chunk_rv_sym")
+    elif storage == "csr":
+        A.set_storage("csr")
+        assert A.get_storage() == "csr"
+    _same(_gpu(ctx, A, b, None, _opts_str(ROUTE_OPTS)), _twin(oracle, name, ROUTE_OPTS))
+
+
+def test_jacobi_is_not_the_unpreconditioned_solve(ctx, oracle):
+    rp, col, val, O, b, _ = _problem(oracle, "random_csr")
+    n = O.shape[0]
+    A = Mat.from_csr(ctx, n, n, rp, col, val)
+    xj, rj = _gpu(ctx, A, b, None, _opts_str(ROUTE_OPTS))
+    xn, rn = _gpu(ctx, A, b, None, _opts_str(ROUTE_OPTS, "none"))
+    xo, ro = oracle.gmres(O, b, reduce_mode=oracle.REDUCE_DBR, **ROUTE_OPTS)
+    assert np.array_equal(xn, xo) and np.array_equal(rn["hist"], ro["hist"])     # pc none is still the oracle's
+    assert not np.array_equal(xj, xn) and rj["hist"][0] != rn["hist"][0]
+
+
+# ----------------------------------------------------------------------------------------------------------- shapes
+SHAPES = {
+    "odd_n": ("box-13x11x7", dict(restart=5, max_it=57, rtol=1e-30, guess_nonzero=1)),      # n = 1001, bnorm path
+    "two_chunks": ("box-16x16x33", dict(restart=30, max_it=90, rtol=1e-10)),                # n = 8448
+    "restart40": ("box-9x8x7", dict(restart=40, max_it=200, rtol=1e-10)),                   # BuildSoln split, 2 MDots
+    "gmres1": ("box-10x10x10", dict(restart=1, max_it=25, rtol=1e-30, guess_nonzero=1)),
+    "inner": ("box-12x10x11", dict(restart=30, max_it=20, rtol=1e-20, uirnorm=1, guess_nonzero=1)),
+}
+
+
+@pytest.mark.parametrize("case", list(SHAPES))
+def test_shapes_bitwise_vs_twin(ctx, oracle, case):
+    name, o = SHAPES[case]
+    rp, col, val, O, b, _ = _problem(oracle, name)
+    n = O.shape[0]
+    x0 = _x0(n) if o.get("guess_nonzero") else None
+    A = Mat.from_csr(ctx, n, n, rp, col, val)
+    want = _twin(oracle, name, o, x0)
+    assert want[1]["its"] > 0
+    _same(_gpu(ctx, A, b, x0, _opts_str(o)), want)
+
+
+# ---------------------------------------------------------------------------------- the scaling identity on the device
+@pytest.mark.parametrize("uirnorm", [0, 1])
+def test_scaling_identity_against_the_c_oracle(ctx, oracle, uirnorm):
+    """2D Poisson, diagonal 4.0: the Jacobi solve is the unpreconditioned C oracle's with the history times 0.25."""
+    O, b, x0, _ = poisson2d_identity_problem(oracle)
+    kw = dict(IDENTITY_OPTS, uirnorm=uirnorm)
+    xo, ro = oracle.gmres(O, b, x0=x0, reduce_mode=oracle.REDUCE_DBR, **kw)
+    A = Mat.box_stencil(ctx, 2, 40, 33)
+    xg, rg = _gpu(ctx, A, b, x0, _opts_str(kw))
+    assert (rg["its"], rg["reason"]) == (ro["its"], ro["reason"])
+    assert np.array_equal(rg["hist"], 0.25 * ro["hist"]) and rg["rnorm"] == 0.25 * ro["rnorm"]
+    assert np.array_equal(xg, xo)
+
+
+# ------------------------------------------------------------------------------------------- special diagonal entries
+def _special_diagonal(kind):
+    """The random CSR (n = 1001) with rows 3, 500 and 1000 changed: "zero": a stored 0.0, a stored -0.0 and the
+    diagonal entry removed; "subnormal": a_33 = 5e-324."""
+    rp, col, val = _random_csr(np.random.default_rng(77), 1001, 6)
+    rows = np.repeat(np.arange(1001), np.diff(rp))
+    val = val.copy()
+    diag = np.flatnonzero(col == rows)
+    if kind == "subnormal":
+        val[diag[3]] = 5e-324
+        return rp, col, val
+    val[diag[3]], val[diag[500]] = 0.0, -0.0
+    keep = np.ones(col.size, bool)
+    keep[diag[1000]] = False
+    rows, col, val = rows[keep], col[keep], val[keep]
+    rp = np.concatenate([[0], np.cumsum(np.bincount(rows, minlength=1001))]).astype(np.int32)
+    return rp, col, val
+
+
+@pytest.mark.parametrize("kind", ["zero", "subnormal"])
+def test_zero_absent_and_subnormal_diagonal_entries(ctx, oracle, kind):
+    rp, col, val = _special_diagonal(kind)
+    n = 1001
+    O = oracle.Mat.from_arrays(n, n, rp, col, val)
+    A = Mat.from_csr(ctx, n, n, rp, col, val)
+    b = np.random.default_rng(5).uniform(-1, 1, n)
+    dinv = pt.jacobi_dinv(rp, col, val)
+    o = dict(restart=10, max_it=30, rtol=1e-12)
+    want = pt.gmres(O, b, dinv, **o)
+    if kind == "zero":
+        assert dinv[3] == dinv[500] == dinv[1000] == 1.0 and want[1]["its"] > 0
+    else:
+        assert dinv[3] == np.inf and want[1]["reason"] == DIVERGED_NANORINF
+    _same(_gpu(ctx, A, b, None, _opts_str(o)), want)
+
+
+# ---------------------------------------------------------------------------------------------------- MatGetDiagonal
+def test_get_diagonal_bitwise_for_every_storage(ctx, oracle):
+    # a box stencil assembled by the caller: csr, dv (a 7-pair dictionary fits) and, on per-row values, stencil
+    rp, col, val = oracle.poisson3d_rows(64, 64, 2, 0, 2).arrays()
+    n = len(rp) - 1
+    A = Mat.from_csr(ctx, n, n, rp, col, val)
+    for storage in ("dv", "csr"):
+        A.set_storage(storage)
+        assert A.get_storage() == storage
+        assert np.array_equal(A.get_diagonal().get_array().view(np.uint64), pt.diagonal(rp, col, val).view(np.uint64))
+    rp, col, val, O, _, _ = _problem(oracle, "box-64x64x2")
+    A = Mat.from_csr(ctx, n, n, rp, col, val)
+    assert A.get_storage() == "stencil"
+    assert np.array_equal(A.get_diagonal().get_array(), pt.diagonal(rp, col, val))
+    # generated boxes keep their CSR; a row with no stored diagonal reads 0.0, a stored -0.0 keeps its sign
+    G = Mat.box_convdiff(ctx, 3, 17, 16, 16, False, False, (0.5, -0.25, 0.125))
+    assert np.array_equal(G.get_diagonal().get_array(), pt.diagonal(*_problem(oracle, "convdiff")[:3]))
+    rp, col, val = _special_diagonal("zero")
+    d = Mat.from_csr(ctx, 1001, 1001, rp, col, val).get_diagonal().get_array()
+    assert np.array_equal(d.view(np.uint64), pt.diagonal(rp, col, val).view(np.uint64))
+    assert d[1000] == 0.0 and np.signbit(d[500]) and not np.signbit(d[3])
+
+
+def test_get_diagonal_refusals(ctx, oracle):
+    def code(f):
+        with pytest.raises(MsplitError) as e:
+            f()
+        return e.value.code
+
+    assert code(lambda: Mat.box_matfree(ctx, 3, 9, 8, 7).get_diagonal()) == ERR_SUP
+    R = Mat.box_stencil(ctx, 3, 9, 8, 7)
+    assert R.get_storage() == "dv"
+    R.get_diagonal()
+    R.release_csr()
+    assert code(lambda: R.get_diagonal()) == ERR_SUP
+    rows = Mat.from_csr_rows(ctx, 6, 6, [1, 4], [0, 1, 2], [1, 4], [2.0, 3.0])
+    assert code(lambda: rows.get_diagonal()) == ERR_SUP
+    wide = Mat.from_csr(ctx, 2, 3, [0, 1, 2], [0, 1], [1.0, 1.0])
+    assert code(lambda: wide.get_diagonal(Vec(ctx, 2))) == ERR_ARG_SIZ
+    # and a KSP under Jacobi refuses such an operator at set-up, naming the cause
+    ksp = KSP(ctx)
+    ksp.set_operators(R)
+    ksp.set_pc_type("jacobi")
+    assert code(ksp.set_up) == ERR_SUP
+
+
+# ----------------------------------------------------------------------------------------------- graphs and switching
+def test_graph_replay_equals_eager(ctx, oracle):
+    """MSPLIT_GRAPHS=0 and the default give the same bits; the second solve on one KSP replays the captured cycles."""
+    name = "box-17x16x16"
+    rp, col, val, O, b, _ = _problem(oracle, name)
+    n = O.shape[0]
+    A = Mat.from_csr(ctx, n, n, rp, col, val)
+    want = _twin(oracle, name, ROUTE_OPTS)
+
+    def twice(graphs):
+        os.environ["MSPLIT_GRAPHS"] = "1" if graphs else "0"
+        try:
+            ksp = KSP(ctx)
+            ksp.set_operators(A)
+            ksp.set_from_options(Options(_opts_str(ROUTE_OPTS)))
+            bv, xv = Vec.from_array(ctx, b), Vec(ctx, n)
+            out = []
+            for _ in range(2):
+                ksp.solve(bv, xv)
+                out.append(_result(ksp, xv))
+            return out
+        finally:
+            os.environ.pop("MSPLIT_GRAPHS", None)
+
+    for got in twice(False) + twice(True):
+        _same(got, want)
+
+
+def test_switching_pc_and_operator_on_one_ksp(ctx, oracle):
+    name = "box-17x16x16"
+    rp, col, val, O, b, _ = _problem(oracle, name)
+    n = O.shape[0]
+    A = Mat.from_csr(ctx, n, n, rp, col, val)
+    wj = _twin(oracle, name, ROUTE_OPTS)
+    wn = oracle.gmres(O, b, reduce_mode=oracle.REDUCE_DBR, **ROUTE_OPTS)
+    ksp = KSP(ctx)
+    ksp.set_operators(A)
+    ksp.set_from_options(Options(_opts_str(ROUTE_OPTS, "none")))
+    assert ksp.get_pc_type() == "none"
+    for word, want in (("none", wn), ("jacobi", wj), ("none", wn), ("jacobi", wj)):
+        ksp.set_pc_type(word)
+        assert ksp.get_pc_type() == word
+        _same(_solve_on(ksp, ctx, A, b, None), want)
+    # another operator of the same size: PCSetUp runs again
+    rp2, col2, val2, O2, b2, _ = _problem(oracle, "box-17x16x16-unsym")
+    val3 = val2.copy()
+    rows = np.repeat(np.arange(n), np.diff(rp2))
+    val3[col2 == rows] *= np.random.default_rng(3).uniform(1.0, 4.0, n)
+    A3 = Mat.from_csr(ctx, n, n, rp2, col2, val3)
+    ksp.set_operators(A3)
+    want3 = pt.gmres(oracle.Mat.from_arrays(n, n, rp2, col2, val3), b2, pt.jacobi_dinv(rp2, col2, val3), **ROUTE_OPTS)
+    _same(_solve_on(ksp, ctx, A3, b2, None), want3)
+
+
+# ---------------------------------------------------------------------------------------------------------- exclusions
+@pytest.mark.parametrize("extra", ["-ksp_pc_side right", "-ksp_pc_side symmetric", "-ksp_norm_type unpreconditioned",
+                                   "-pc_jacobi_type rowmax", "-pc_jacobi_type rowsum", "-pc_jacobi_type rowl1",
+                                   "-pc_jacobi_abs"])
+def test_option_exclusions_raise_err_sup(ctx, extra):
+    ksp = KSP(ctx)
+    with pytest.raises(MsplitError) as e:
+        ksp.set_from_options(Options("-pc_type jacobi " + extra))
+    assert e.value.code == ERR_SUP and extra.split()[0].lstrip("-") in str(e.value)
+    assert ksp.get_pc_type() == "none"
+    # with pc none the same options change nothing
+    ksp.set_from_options(Options("-pc_type none " + extra))
+    assert ksp.get_pc_type() == "none"
+    # and what jacobi does accept
+    ksp.set_from_options(Options("-pc_type jacobi -ksp_pc_side left -ksp_norm_type preconditioned "
+                                 "-pc_jacobi_type diagonal"))
+    assert ksp.get_pc_type() == "jacobi"
+
+
+def test_other_preconditioners_and_values_stay_rejected(ctx):
+    ksp = KSP(ctx)
+    for word in ("ilu", "bjacobi", "sor"):
+        with pytest.raises(MsplitError) as e:
+            ksp.set_from_options(Options(f"-pc_type {word}"))
+        assert e.value.code == ERR_SUP
+    with pytest.raises(MsplitError):
+        ksp.set_pc_type("ilu")
+    assert _lib.load().msp_ksp_set_pc_type(ksp.h, C.c_int(2)) == ERR_ARG_OUTOFRANGE
+    assert _lib.load().msp_ksp_set_pc_type(ksp.h, C.c_int(-1)) == ERR_ARG_OUTOFRANGE
+    assert ksp.get_pc_type() == "none"
+
+
+@pytest.mark.parametrize("how", ["single", "block16", "seq"])
+def test_rounded_bases_and_seq_reduction_refused_at_solve(ctx, oracle, how):
+    name, o = SHAPES["restart40"]
+    rp, col, val, O, b, _ = _problem(oracle, name)
+    n = O.shape[0]
+    A = Mat.from_csr(ctx, n, n, rp, col, val)
+    ksp = KSP(ctx)
+    ksp.set_operators(A)
+    ksp.set_from_options(Options(_opts_str(o)))
+    before = ctx.get_reduction()
+    if how == "seq":
+        ctx.set_reduction("seq")
+    else:
+        ksp.set_basis_precision(how)
+    try:
+        with pytest.raises(MsplitError) as e:
+            _solve_on(ksp, ctx, A, b, None)
+        assert e.value.code == ERR_SUP
+    finally:
+        ctx.set_reduction(before)
+    assert ctx.get_reduction() == before == "dbr"
+    ksp.set_basis_precision("double")
+    _same(_solve_on(ksp, ctx, A, b, None), _twin(oracle, name, o))                # and the KSP still serves
+
+
+# ---------------------------------------------------------------------------------------------------------- work bytes
+def test_work_bytes_add_the_inverse_diagonal(ctx, oracle):
+    """On the random CSR pc none takes the stored-W step: Jacobi holds the same basis, W and recurrence block, and n
+    doubles more."""
+    rp, col, val, O, b, _ = _problem(oracle, "random_csr")
+    n = O.shape[0]
+    A = Mat.from_csr(ctx, n, n, rp, col, val)
+    got = {}
+    for pc in ("none", "jacobi"):
+        ksp = KSP(ctx)
+        ksp.set_operators(A)
+        ksp.set_from_options(Options(_opts_str(ROUTE_OPTS, pc)))
+        assert ksp.get_work_bytes() == 0
+        ksp.solve(Vec.from_array(ctx, b), Vec(ctx, n))
+        got[pc] = ksp.get_work_bytes()
+    stride = (n + 511) // 512 * 512
+    assert got["none"] >= 8 * (31 * stride + n)                                   # the basis and W are in there
+    assert got["jacobi"] == got["none"] + 8 * n
+
+
+# ----------------------------------------------------------------------------------------------------- guarded operands
+@pytest.mark.parametrize("name", ["box-13x11x7", "box-17x16x16"])
+def test_guarded_16_byte_aligned_operands(ctx, oracle, name):
+    """b and x as windows that are 16-byte but not 32-byte aligned, NaN guard bands around them; a nonzero guess
+    without uirnorm, so ||dinv .* b|| reads b through k_pcj_apply_norm too."""
+    rp, col, val, O, b, _ = _problem(oracle, name)
+    n = O.shape[0]
+    o = dict(restart=5, max_it=17, rtol=1e-30, guess_nonzero=1)
+    x0 = _x0(n)
+    A = Mat.from_csr(ctx, n, n, rp, col, val)
+    gb, gx = Guarded.input(ctx, b, 514), Guarded.input(ctx, x0, 514)
+    ksp = KSP(ctx)
+    ksp.set_operators(A)
+    ksp.set_from_options(Options(_opts_str(o)))
+    ksp.solve(gb.vec, gx.vec)
+    _same(_result(ksp, gx.vec), _twin(oracle, name, o, x0))
+    assert np.array_equal(gb.get_array().view(np.uint64), b.view(np.uint64))       # b is read only
+    check_all(gb, gx)
+
+
+# ------------------------------------------------------------------------------------------------------------ SM driver
+def test_sm_driver_with_jacobi_inner_solves(ctx):
+    """sm_solve on two blocks of the 12x10x8 convection-diffusion box, the inner GMRES(30)s (max_it 20) under
+    -innerK_pc_type jacobi: the driver stops by its own true-residual test and a rerun gives the same bits."""
+    rtol, nb = 1e-6, 2
+
+    def run():
+        opts = Options(" ".join(f"-inner{k + 1}_ksp_max_it 20 -inner{k + 1}_ksp_rtol 1e-20 -inner{k + 1}_pc_type jacobi"
+                                for k in range(nb)))
+        comm = LocalComm()
+        blocks = make_blocks(ctx, 3, 12, 10, 8, nb, range(nb), opts, comm, peclet=(0.5, -0.25, 0.125))
+        assert all(blk.ksp.get_pc_type() == "jacobi" for blk in blocks)
+        res = sm_solve(blocks, comm, rtol=rtol, max_outer=200)
+        return res, np.concatenate([blk.x.get_array() for blk in blocks])
+
+    r1, x1 = run()
+    r2, x2 = run()
+    assert r1.outer_its < 200 and r1.hist[-1] <= rtol * r1.norm0    # stopped by the driver's f64 residual test
+    assert r1.outer_its == r2.outer_its and np.array_equal(np.array(r1.hist), np.array(r2.hist))
+    assert np.array_equal(np.array(r1.inner_its), np.array(r2.inner_its)) and np.array_equal(x1, x2)
