@@ -225,6 +225,17 @@ static int ksp_from_options(msp_ksp *k, const msd_options *o, const char *p, msp
       return MSP_ERR_ARG_OUTOFRANGE;
     }
   }
+  /* -<prefix>msplit_operator_precision double|single: the Arnoldi products read a float copy of a CSR-storage
+   * operator's values (msp_ksp_set_operator_precision) */
+  const char *op = msd_opt_str(o, p, "msplit_operator_precision", NULL);
+  if (op) {
+    if (!strcasecmp(op, "single")) CK(msp_ksp_set_operator_precision(k, MSP_OPER_F32));
+    else if (!strcasecmp(op, "double")) CK(msp_ksp_set_operator_precision(k, MSP_OPER_F64));
+    else {
+      fprintf(stderr, "-%smsplit_operator_precision %s: expected double or single\n", p, op);
+      return MSP_ERR_ARG_OUTOFRANGE;
+    }
+  }
   return MSP_SUCCESS;
 }
 

@@ -219,6 +219,9 @@ int msp_mat_get_csr(const msp_mat *A, int32_t *rowptr, int32_t *col, double *val
  * storage its products read.  MSP_ERR_SUP for a row-compressed matrix (msp_mat_create_csr_rows), a matrix-free box
  * and a matrix after msp_mat_release_csr; MSP_ERR_ARG_SIZ for a non-square matrix or a d of another size. */
 int msp_mat_get_diagonal(const msp_mat *A, msp_vec *d);
+/* Device bytes of the single-precision copy of the values that MSP_OPER_F32 solves read
+ * (msp_ksp_set_operator_precision): 0 until a solve has built it, then 8 (nnz + 2). */
+int msp_mat_get_value_copy_bytes(const msp_mat *A, int64_t *bytes);
 /* MatMult y = A x (utils.c:626; KSP_PCApplyBAorAB inside KSPGMRESCycle). */
 int msp_mat_mult(msp_mat *A, const msp_vec *x, msp_vec *y);
 /* MatResidual r = b - A x (utils.c:549, :565, :579, :946;
@@ -356,6 +359,36 @@ int msp_ksp_get_work_bytes(const msp_ksp *ksp, int64_t *bytes);
 #define MSP_PC_JACOBI 1
 int msp_ksp_set_pc_type(msp_ksp *ksp, int pc_type);
 int msp_ksp_get_pc_type(const msp_ksp *ksp, int *pc_type);
+/* Storage precision of the operator's values in the Arnoldi products (-msplit_operator_precision double|single).
+ * MSP_OPER_F64 (default): every product reads the operator as it is stored; nothing changes.
+ * MSP_OPER_F32: compressed-operator GMRES for an operator whose products read its CSR arrays (MSP_STORAGE_CSR).
+ * The Arnoldi products W = A (sc[it] v) of this KSP read a copy A~ of the operator:
+ *   - every stored value is rounded once, a~ = (float)a: round to nearest even, gradual underflow (MSP_BASIS_F32's
+ *     conversion), and packed with its column into one 8-byte word, 8 bytes per entry streamed for 12;
+ *   - a row is summed exactly as the f64 MatMult sums it: s = s + (double)a~_k * (x[c_k] * sc), entries in CSR
+ *     order, f64, never contracted -- so the product is, bit for bit, the f64 kernel's product on the matrix whose
+ *     values are (double)(float)a.
+ * Everything else reads the f64 operator: KSPInitialResidual at every restart, msp_mat_mult, msp_mat_residual,
+ * R = A S, msp_mat_get_diagonal and Jacobi's dinv.  The solve is therefore GMRES on A~ with an f64 residual
+ * correction at each restart.  Inside one restart cycle the recurrence residual is A~'s residual, and the true
+ * residual can differ from it by about 2^-24 || |A| |dx| ||; from a zero guess within one cycle, x solves the
+ * rounded system.  A tolerance below that is met only across restarts.
+ * The copy belongs to the matrix: the first solve that needs it builds it, a storage switch in between makes the
+ * next solve rebuild it, and it is freed with the matrix.  The f64 arrays stay, so the matrix holds 8 bytes per
+ * entry more (msp_mat_get_value_copy_bytes: 0 until the copy is built, then 8 (nnz + 2)).
+ * A finite value whose float is not finite (|a| > FLT_MAX) is an error: the solve returns MSP_ERR_ARG_OUTOFRANGE
+ * and the message gives the count; no copy is kept and the matrix stays usable with MSP_OPER_F64.  NaN and +-inf
+ * entries pass through as they are.
+ * Works with the three basis precisions and with MSP_PC_NONE / MSP_PC_JACOBI (Jacobi on the double basis, as
+ * ever): only the MatMult of a stored-W step is replaced.  The solve returns MSP_ERR_SUP, naming the cause, on a
+ * context in MSP_REDUCE_SEQ and for an operator whose products do not read the CSR arrays -- MSP_STORAGE_DV,
+ * MSP_STORAGE_STENCIL, matrix-free, row-compressed, or a released CSR; msp_mat_set_storage(A, MSP_STORAGE_CSR)
+ * is the way there for a matrix that holds its CSR.  Changing the precision drops the captured cycles and nothing
+ * else.  Any other value: MSP_ERR_ARG_OUTOFRANGE. */
+#define MSP_OPER_F64 0
+#define MSP_OPER_F32 1
+int msp_ksp_set_operator_precision(msp_ksp *ksp, int prec);
+int msp_ksp_get_operator_precision(const msp_ksp *ksp, int *prec);
 
 /* ------------------------------------------------------------------ dense */
 /* A block of rows of a MATDENSE / MATMPIDENSE matrix, column-major in HBM with

@@ -112,6 +112,9 @@ _SIGS = {
     "msp_ksp_set_pc_type": [_vp, C.c_int],
     "msp_ksp_get_pc_type": [_vp, _P(C.c_int)],
     "msp_mat_get_diagonal": [_vp, _vp],
+    "msp_ksp_set_operator_precision": [_vp, C.c_int],
+    "msp_ksp_get_operator_precision": [_vp, _P(C.c_int)],
+    "msp_mat_get_value_copy_bytes": [_vp, _P(C.c_int64)],
     "msp_mat_create_box_stencil_ext": [_vp, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                        _P(_vp)],
     "msp_mat_create_box_matfree": [_vp, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp,

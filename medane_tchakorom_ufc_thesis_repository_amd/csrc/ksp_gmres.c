@@ -51,6 +51,16 @@
  *            kernels form dinv .* W in registers as they load it (8 more bytes per row each, no rewrite of W).  The
  *            cycle's first kernel multiplies the initial residual by dinv in place; ||dinv .* b|| serves the
  *            convergence test's rnorm0.  Neither opfuse nor wfree is taken; the recurrence is unchanged.
+ *   oper f32 MSP_OPER_F32 (msp_ksp_set_operator_precision), an operator whose products read its CSR arrays: the
+ *            Arnoldi MatMult of a stored-W step (the f64, f32, block16 or jacobi one) reads a copy of the operator
+ *            whose values are floats packed with their columns, 8 bytes per entry for 12 (msplit_csr32.hip,
+ *            mspi_spmv_scaled_p32), and sums every row in f64 in the same order: the f64 MatMult on the matrix
+ *            (double)(float)a, bit for bit.  Always MatMult, MDot, MAXPY as three kernels: neither opfuse nor wfree,
+ *            nor the fused MatMult + MDot.  KSPInitialResidual at every restart, MatMult outside the step, the
+ *            diagonal and Jacobi's dinv read the f64 values: the solve is GMRES on the rounded operator with an f64
+ *            residual correction at each restart.  Inside one cycle the recurrence residual is the rounded
+ *            operator's and can differ from the true one by about 2^-24 || |A| |dx| ||; from a zero guess within
+ *            one cycle, x solves the rounded system.
  *
  * Data layout: VV(0..min(m, max_it)) are one allocation of (min(m, max_it)+1) x stride elements; stride = n rounded
  * up to 512 doubles, to 1024 floats or to 2048 int16 (4 KiB each way); block16 keeps its int32 exponents,
@@ -96,6 +106,7 @@ struct msp_ksp {
   int pc_type;              /* MSP_PC_NONE / MSP_PC_JACOBI */
   double *dinv;             /* device, Jacobi: n doubles, 1 / a_ii by PCSetUp's rule */
   int dinv_valid;           /* dinv holds the current operator's (reset by msp_ksp_set_operators) */
+  int oper_prec;            /* MSP_OPER_F64 / MSP_OPER_F32: what the Arnoldi MatMult reads */
   size_t basis_bytes, gblock_bytes, vec_bytes; /* sizes of the allocations (vec_bytes: tmp and cur, each) */
   mspi_gmres_dev g;         /* device-resident recurrence state and arrays */
   void *gblock;             /* the single device allocation behind g */
@@ -279,6 +290,32 @@ int msp_ksp_get_pc_type(const msp_ksp *k, int *pc_type) {
   return MSP_SUCCESS;
 }
 
+int msp_ksp_set_operator_precision(msp_ksp *k, int prec) {
+  if (!k) {
+    mspi_set_error(MSP_ERR_ARG_NULL, "NULL argument");
+    return MSP_ERR_ARG_NULL;
+  }
+  if (prec != MSP_OPER_F64 && prec != MSP_OPER_F32) {
+    mspi_set_error(MSP_ERR_ARG_OUTOFRANGE, "operator precision %d is neither MSP_OPER_F64 nor MSP_OPER_F32", prec);
+    return MSP_ERR_ARG_OUTOFRANGE;
+  }
+  if (prec != k->oper_prec) { /* another MatMult kernel in every captured cycle; the work vectors stay */
+    msp_ctx_synchronize(k->ctx);
+    ksp_drop_graphs(k);
+  }
+  k->oper_prec = prec;
+  return MSP_SUCCESS;
+}
+
+int msp_ksp_get_operator_precision(const msp_ksp *k, int *prec) {
+  if (!k || !prec) {
+    mspi_set_error(MSP_ERR_ARG_NULL, "NULL argument");
+    return MSP_ERR_ARG_NULL;
+  }
+  *prec = k->oper_prec;
+  return MSP_SUCCESS;
+}
+
 int msp_ksp_get_work_bytes(const msp_ksp *k, int64_t *bytes) {
   if (!k || !bytes) {
     mspi_set_error(MSP_ERR_ARG_NULL, "NULL argument");
@@ -370,6 +407,10 @@ static int compressed(const msp_ksp *k) { return k->basis_prec != MSP_BASIS_F64;
  * stencil (wfree), or W stored between the MatMult and the CGS kernels (neither).  The W-free choice follows the
  * operator and msk_set_gm_wfree, so it is asked again before every solve. */
 static void step_kind(const msp_ksp *k, int *opfuse, int *wfree) {
+  if (k->oper_prec == MSP_OPER_F32) { /* the packed copy has a MatMult only: a stored-W step */
+    *opfuse = *wfree = 0;
+    return;
+  }
   if (compressed(k)) { /* those kernels read an f64 basis: the f32 / block16 step stores W */
     *opfuse = *wfree = 0;
     return;
@@ -395,6 +436,12 @@ static int ensure_w(msp_ksp *k) {
   return rc;
 }
 
+/* The Arnoldi MatMult of a stored-W step, W = A (sc x): under MSP_OPER_F32 from the packed copy of the operator */
+static int step_matmult(msp_ksp *k, const double *x, const double *sc, const int *stop) {
+  if (k->oper_prec == MSP_OPER_F32) return mspi_spmv_scaled_p32(k->A, x, sc, k->tmp, stop);
+  return mspi_spmv_scaled(k->A, x, sc, NULL, k->tmp, stop);
+}
+
 /* One KSPGMRESCycle from its initial residual in VV(0): VecNormalize (deferred),
  * up to K Arnoldi steps, BuildSoln(it-1) into x.  Enqueued, no host synchronisation. */
 static int enqueue_cycle(msp_ksp *k, double *x, int K) {
@@ -410,7 +457,7 @@ static int enqueue_cycle(msp_ksp *k, double *x, int K) {
     int rc = mspi_pcj_apply_norm(c, VV(k, 0), k->dinv, VV(k, 0), k->n, sumsq, NULL);
     if (!rc) rc = mspi_gm_cycle_start(c, k->g, sumsq);
     for (int it = 0; it < K && !rc; ++it) {
-      rc = mspi_spmv_scaled(k->A, VV(k, it), sc + it, NULL, k->tmp, stop);
+      rc = step_matmult(k, VV(k, it), sc + it, stop);
       if (!rc) rc = mspi_pcj_mdot(c, k->tmp, k->dinv, it + 1, k->basis, k->stride, sc, k->n, k->g.h, stop);
       if (!rc)
         rc = mspi_pcj_maxpy_norm_update(c, k->tmp, k->dinv, VV(k, it + 1), it + 1, k->basis, k->stride, sc, k->n,
@@ -431,7 +478,7 @@ static int enqueue_cycle(msp_ksp *k, double *x, int K) {
   for (int it = 0; it < K && !rc && f32; ++it) {
     /* W = A (sc[it] s_it) from the current vector (s_it as doubles), h = W . sc.VV(0..it) over the float basis,
      * then s_{it+1} = rnd(W - sum h_j sc[j] VV(j)) to VV(it+1) and back into the current vector, ||s_{it+1}||^2 */
-    rc = mspi_spmv_scaled(k->A, k->cur, sc + it, NULL, k->tmp, stop);
+    rc = step_matmult(k, k->cur, sc + it, stop);
     if (!rc) rc = mspi_cb_mdot(c, k->tmp, it + 1, VF(k, 0), k->stride, sc, k->n, k->g.h, stop);
     if (!rc)
       rc = mspi_cb_maxpy_norm_update(c, k->tmp, k->cur, VF(k, it + 1), it + 1, VF(k, 0), k->stride, sc, k->n, k->g,
@@ -443,7 +490,7 @@ static int enqueue_cycle(msp_ksp *k, double *x, int K) {
     return rc;
   }
   for (int it = 0; it < K && !rc && b16; ++it) { /* the f32 step, the basis read and written as block16 */
-    rc = mspi_spmv_scaled(k->A, k->cur, sc + it, NULL, k->tmp, stop);
+    rc = step_matmult(k, k->cur, sc + it, stop);
     if (!rc) rc = mspi_cb16_mdot(c, k->tmp, it + 1, VH(k, 0), k->stride, EX(k, 0), sc, k->n, k->g.h, stop);
     if (!rc)
       rc = mspi_cb16_maxpy_norm_update(c, k->tmp, k->cur, VH(k, it + 1), EX(k, it + 1), it + 1, VH(k, 0), k->stride,
@@ -473,9 +520,11 @@ static int enqueue_cycle(msp_ksp *k, double *x, int K) {
   for (int it = 0; it < K && !rc && !opfuse && !wfree; ++it) {
     /* W = A (sc[it] VV(it))  (KSP_PCApplyBAorAB with PCNONE on the normalised VV(it)),
      * CGS: h = VecMDot(W, VV(0..it)) -- one fused launch where the operator allows */
-    rc = mspi_spmv_mdot(k->A, VV(k, it), sc + it, k->tmp, it + 1, k->basis, k->stride, sc, k->g.h, stop);
+    rc = k->oper_prec == MSP_OPER_F32 ? MSP_ERR_SUP /* the fused kernel reads the f64 values */
+                                      : mspi_spmv_mdot(k->A, VV(k, it), sc + it, k->tmp, it + 1, k->basis, k->stride,
+                                                       sc, k->g.h, stop);
     if (rc == MSP_ERR_SUP) {
-      rc = mspi_spmv_scaled(k->A, VV(k, it), sc + it, NULL, k->tmp, stop);
+      rc = step_matmult(k, VV(k, it), sc + it, stop);
       if (!rc) rc = mspi_mdot_basis(c, k->tmp, it + 1, k->basis, k->stride, sc, k->n, k->g.h, stop);
     }
     /* then VV(it+1) = W - sum h_j VV(j); ||VV(it+1)||^2 */
@@ -500,7 +549,8 @@ static int run_cycle(msp_ksp *k, double *x, int K) {
   int rc = mspi_reserve_partial(c, k->n); /* before the lookup: it may reallocate (a new epoch) */
   if (rc) return rc;
   const uint64_t aver = mspi_mat_version(k->A), epoch = mspi_ctx_epoch(c);
-  /* the basis precision is not in the key: changing it frees the work, and with it every captured cycle */
+  /* the basis precision is not in the key: changing it frees the work, and with it every captured cycle; changing
+   * the operator precision drops the captured cycles */
   const int tuning = msk_get_tuning(), shape = msk_get_shape_epoch();
   for (int i = 0; i < KSP_NGRAPH; ++i) {
     const ksp_graph *g = &k->graphs[i];
@@ -567,7 +617,15 @@ int msp_ksp_solve(msp_ksp *k, const msp_vec *b, msp_vec *x) {
     mspi_set_error(MSP_ERR_SUP, "MSP_PC_JACOBI needs the DBR reduction: its fused kernels have no MSP_REDUCE_SEQ form");
     return MSP_ERR_SUP;
   }
+  if (k->oper_prec == MSP_OPER_F32 && mspi_reduce_seq(k->ctx)) {
+    mspi_set_error(MSP_ERR_SUP, "MSP_OPER_F32 needs the DBR reduction: MSP_REDUCE_SEQ reproduces PETSc's f64 solve bit "
+                                "for bit, which a rounded operator cannot");
+    return MSP_ERR_SUP;
+  }
   int rc = mspi_set_device(k->ctx);
+  /* the packed copy, built or rebuilt before any capture; an operator whose products do not read its CSR arrays
+   * and values beyond the float range are refused here, before any work is allocated */
+  if (!rc && k->oper_prec == MSP_OPER_F32) rc = mspi_mat_ensure_p32(k->A);
   if (!rc) rc = msp_ksp_set_up(k);
   if (!rc) rc = ensure_w(k);
   if (rc) return rc;

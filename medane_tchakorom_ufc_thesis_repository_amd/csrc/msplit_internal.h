@@ -221,6 +221,13 @@ int mspi_pcj_mdot(msp_ctx *ctx, const double *w, const double *dinv, int nv, con
 int mspi_pcj_maxpy_norm_update(msp_ctx *ctx, const double *win, const double *dinv, double *vout, int nv,
                                const double *base, int64_t stride, const double *scale, int64_t n, mspi_gmres_dev g,
                                int m, const int *stop);
+/* ---- MSP_OPER_F32: the Arnoldi MatMult over a single-precision copy of the CSR values (msplit_csr32.hip) ---- */
+/* Build the copy, or rebuild a stale one (keyed to mspi_mat_version); allocates and synchronises, so never inside a
+   graph capture.  MSP_ERR_SUP unless A's products read its CSR arrays (naming the storage), MSP_ERR_ARG_OUTOFRANGE
+   with the count when finite values overflow the float range (no copy is kept). */
+int mspi_mat_ensure_p32(msp_mat *A);
+/* y = A~ (sdev[0] x): bit for bit mspi_spmv_scaled on a matrix whose values are (double)(float)a; honours stop */
+int mspi_spmv_scaled_p32(msp_mat *A, const double *x, const double *sdev, double *y, const int *stop);
 /* ---- the GMRES step's MatMult inside the CGS kernels (A in DV storage, 8-code ELL layout) ---- */
 int mspi_op_fusable(const msp_mat *A);
 /* h(0..nv-1) = (A (sdev[0] x)) . scale_j VV(j): stage 1 computes each row of A(sc x) in registers */

@@ -35,6 +35,32 @@ __device__ __forceinline__ int4 ld_nt(const int4* p) {
   return make_int4(v.x, v.y, v.z, v.w);
 }
 
+// ---------------------------------------------- the CSR MatMults' row-block schedule and LDS-DMA staging
+// (msplit_kernels.hip: k_spmv_lds8 and the box kernels; msplit_csr32.hip: k_spmv_p32).  The XCD-aware order is
+// described with the SpMV kernels in msplit_kernels.hip; only the schedule changes, every row's sum is the same.
+struct XcdMap {
+  int32_t bp;  // row blocks per plane (0: identity order)
+  int32_t gb;  // row blocks per group, (bp / gb) % 8 == 0
+  int32_t np;  // planes
+};
+
+__device__ __forceinline__ int32_t row_block(XcdMap m) {
+  const int32_t i = blockIdx.x;
+  if (m.bp == 0) return i;
+  if (m.bp < 0) return (i & 7) * m.np + (i >> 3);  // z-chunks: XCD x sweeps rows [x N/8, (x+1) N/8) in order
+  const int32_t xcd = i & 7, j = i >> 3;
+  const int32_t span = m.np * m.gb;  // blocks of one group over all planes
+  const int32_t q = j / span, rem = j - q * span;
+  const int32_t k = rem / m.gb, t = rem - k * m.gb;
+  return k * m.bp + (xcd + 8 * q) * m.gb + t;
+}
+
+// aux (cache policy) 2 = nt on gfx950 (global_load_lds_dwordx4 ... nt)
+template <bool NT>
+__device__ __forceinline__ void glds16(const void* g, void* lds) {
+  __builtin_amdgcn_global_load_lds(g, (__attribute__((address_space(3))) void*)lds, 16, 0, NT ? 2 : 0);
+}
+
 __device__ __forceinline__ const double* vec_at(const Vecs& V, int j) {
   return V.base ? V.base + (int64_t)j * V.stride : V.p[j];
 }
@@ -286,6 +312,9 @@ __device__ __forceinline__ double group_sum(const double (&a)[G], const double (
 // ===================================================================== launchers
 // Tuning flags (A/B experiments; MSPLIT_TUNING at context creation), defined in msplit_kernels.hip.
 extern __attribute__((visibility("hidden"))) int msk_tuning_flags;
+
+// The row-block schedule msk_spmv gives an operator of this shape, {bp, gb, np} of XcdMap (msplit_kernels.hip)
+__attribute__((visibility("hidden"))) void msk_xcd_map3(int32_t nrows, int64_t plane, int32_t out[3]);
 
 // The A/B variants of MDot stage 1 (msplit_k_dot_a.hip, msplit_k_dot_b.hip), for msk_dot_stage1 (msplit_k_dot.hip).
 __attribute__((visibility("hidden"))) int msk_dot1_variants_a(int var, int nv, const double* w, const Vecs& V,

@@ -244,4 +244,12 @@ int msk_pcj_mdot(const double* w, const double* dinv, const double* vb, int64_t 
 int msk_pcj_maxpy_norm(const double* win, const double* dinv, double* vout, const double* vb, int64_t stride,
                        const double* scale, const double* adev, int nv, int64_t n, double* partial, const int* stop,
                        hipStream_t s);
+// ---- the single-precision copy of a CSR operator's values (msplit_csr32.hip): nnz + 2 words {int32 col, float val}
+// in CSR order, 16-byte aligned; the two slack words are written too.  *over (zeroed by the caller) counts the
+// finite values whose float is not finite.
+int msk_csr32_pack(int64_t nnz, const int32_t* col, const double* val, void* pk, unsigned int* over, hipStream_t s);
+// y = A~ (sdev[0] x), every row summed as msk_spmv's SCALED mode sums it with the values (double)(float)a;
+// lds_cap and plane as msk_spmv (lds_cap 0: the direct kernel)
+int msk_spmv_p32(int32_t nrows, const int32_t* rowptr, const void* pk, const double* x, double* y, int32_t lds_cap,
+                 const double* sdev, const int* stop, int64_t plane, hipStream_t s);
 }

@@ -45,32 +45,9 @@ namespace {  // internal linkage: the kernels are launched from this file only
 // gb blocks earlier (~gb*256 rows of traffic ago, inside the 4 MiB L2), and
 // +-1 line stays inside the group.  Only the schedule changes: every row's sum
 // is the same, so results are bitwise unchanged.
-struct XcdMap {
-  int32_t bp;  // row blocks per plane (0: identity order)
-  int32_t gb;  // row blocks per group, (bp / gb) % 8 == 0
-  int32_t np;  // planes
-};
-
-__device__ __forceinline__ int32_t row_block(XcdMap m) {
-  const int32_t i = blockIdx.x;
-  if (m.bp == 0) return i;
-  if (m.bp < 0) return (i & 7) * m.np + (i >> 3);  // z-chunks: XCD x sweeps rows [x N/8, (x+1) N/8) in order
-  const int32_t xcd = i & 7, j = i >> 3;
-  const int32_t span = m.np * m.gb;  // blocks of one group over all planes
-  const int32_t q = j / span, rem = j - q * span;
-  const int32_t k = rem / m.gb, t = rem - k * m.gb;
-  return k * m.bp + (xcd + 8 * q) * m.gb + t;
-}
-
 // Stage a row block's val/col slice (16-byte aligned-down views v2/c4 with n2/n4
 // slices) into LDS.  SU > 1: issue SU val and SU/2 col loads per lane before the
 // first LDS write, so staging costs one memory latency instead of one per slice.
-// aux (cache policy) 2 = nt on gfx950 (global_load_lds_dwordx4 ... nt)
-template <bool NT>
-__device__ __forceinline__ void glds16(const void* g, void* lds) {
-  __builtin_amdgcn_global_load_lds(g, (__attribute__((address_space(3))) void*)lds, 16, 0, NT ? 2 : 0);
-}
-
 // SU == 0: LDS-DMA staging.  Each wave-instruction writes 64 consecutive 16-byte
 // slices (LDS destination wave-uniform, source per lane); the tail lanes of the
 // last instruction re-read the last slice into slack LDS, so the LDS capacity is
@@ -2322,6 +2299,14 @@ static inline XcdMap xcd_map(int32_t nrows, int64_t plane) {
   m.gb = gb;
   m.np = (int32_t)(nrows / plane);
   return m;
+}
+
+// The same schedule for the packed-operator MatMult (msplit_csr32.hip): {bp, gb, np} of xcd_map
+__attribute__((visibility("hidden"))) void msk_xcd_map3(int32_t nrows, int64_t plane, int32_t out[3]) {
+  const XcdMap m = xcd_map(nrows, plane);
+  out[0] = m.bp;
+  out[1] = m.gb;
+  out[2] = m.np;
 }
 
 static inline int grid_for(int64_t work, int cap) {

@@ -667,6 +667,10 @@ struct msp_mat {
   int64_t rv_stride = 0;
   bool rv_on = false;
   bool csr_released = false;   // msp_mat_release_csr: col/val freed (and rowptr in the ELL layout)
+  // MSP_OPER_F32's copy of the CSR values (mspi_mat_ensure_p32): nnz + 2 words {int32 col, float val} in CSR order,
+  // built by the first solve that needs it and again when the matrix's version has moved on; col/val stay
+  void* p32 = nullptr;
+  uint64_t p32_version = 0;
   uint64_t version = next_version();  // unique per object and bumped when its products' kernels change
 };
 
@@ -1288,6 +1292,7 @@ extern "C" int msp_mat_destroy(msp_mat** pA) {
   if (A->col) (void)hipFree(A->col);
   if (A->val) (void)hipFree(A->val);
   if (A->row_ids) (void)hipFree(A->row_ids);
+  if (A->p32) (void)hipFree(A->p32);
   rv_free(A);
   dv_free(A);
   msp_ctx* c = A->ctx;
@@ -1675,6 +1680,76 @@ extern "C" int mspi_spmv_scaled(msp_mat* A, const double* x, const double* sdev,
   KTimer kt(c, MSP_KERNEL_SPMV, spmv_bytes(A, false) + (vout ? 8.0 * (double)A->nrows : 0.0));
   KCHK(msk_spmv(A->nrows, A->rowptr, A->col, A->val, x, nullptr, y, A->lds_cap, MSK_SPMV_SCALED, sdev, vout, stop,
                 A->plane, c->stream));
+  return MSP_SUCCESS;
+}
+
+// ---- MSP_OPER_F32 (msplit_csr32.hip): the Arnoldi MatMult over a packed single-precision copy of the CSR values.
+// The copy belongs to the matrix: built by the first solve that needs it (before any graph capture; this call
+// allocates and synchronises), keyed to the matrix's version so that a storage switch in between rebuilds it, freed
+// with the matrix.  The f64 col/val arrays stay -- the restart's residual, MatMult and the diagonal read them -- so
+// the matrix holds 8 bytes per entry more.
+extern "C" int mspi_mat_ensure_p32(msp_mat* A) {
+  ARGCHK(A, MSP_ERR_ARG_NULL, "mat is NULL");
+  const char* st = A->matfree      ? "matrix-free (MSP_STORAGE_NONE)"
+                   : A->compressed ? "row-compressed (msp_mat_create_csr_rows)"
+                   : A->dv_on      ? (A->csr_released ? "MSP_STORAGE_DV with its CSR released" : "MSP_STORAGE_DV")
+                   : A->rv_on      ? "MSP_STORAGE_STENCIL"
+                                   : nullptr;
+  ARGCHK(!st, MSP_ERR_SUP, "MSP_OPER_F32 replaces the MatMult that reads the CSR arrays, and this operator's products "
+         "do not read them: its storage is %s; msp_mat_set_storage(A, MSP_STORAGE_CSR) where the matrix holds its CSR", st);
+  ARGCHK(!A->csr_released && A->rowptr && (A->nnz == 0 || (A->col && A->val)), MSP_ERR_SUP,
+         "MSP_OPER_F32: CSR storage released (msp_mat_release_csr)");
+  ARGCHK(A->nrows == A->ncols, MSP_ERR_SUP, "scaled MatMult needs a square, uncompressed operator");
+  if (A->p32 && A->p32_version == A->version) return MSP_SUCCESS;
+  msp_ctx* c = A->ctx;
+  HIPCHK(hipStreamSynchronize(c->stream));  // a stale copy may still be read by an earlier solve's kernels
+  if (A->p32) HIPCHK(hipFree(A->p32));
+  A->p32 = nullptr;
+  void* pk = nullptr;
+  unsigned int* over = nullptr;
+  HIPCHK(hipMalloc(&pk, (size_t)(A->nnz + 2) * 8));
+  if (hipMalloc((void**)&over, sizeof(unsigned int)) != hipSuccess) {
+    (void)hipFree(pk);
+    mspi_set_error(MSP_ERR_MEM, "MSP_OPER_F32: device allocation failed");
+    return MSP_ERR_MEM;
+  }
+  unsigned int nover = 0;
+  hipError_t e = hipMemsetAsync(over, 0, sizeof(unsigned int), c->stream);
+  if (e == hipSuccess) e = (hipError_t)msk_csr32_pack(A->nnz, A->col, A->val, pk, over, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(&nover, over, sizeof(nover), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  (void)hipFree(over);
+  if (e != hipSuccess || nover) {
+    (void)hipFree(pk);
+    if (e != hipSuccess) {
+      mspi_set_error(MSP_ERR_LIB, "MSP_OPER_F32: packing the operator failed: %s", hipGetErrorString(e));
+      return MSP_ERR_LIB;
+    }
+    mspi_set_error(MSP_ERR_ARG_OUTOFRANGE, "MSP_OPER_F32: %u finite value%s of the operator exceed%s the float range "
+                   "(|a| > FLT_MAX); the matrix stays usable with MSP_OPER_F64", nover, nover == 1 ? "" : "s",
+                   nover == 1 ? "s" : "");
+    return MSP_ERR_ARG_OUTOFRANGE;
+  }
+  A->p32 = pk;
+  A->p32_version = A->version;
+  return MSP_SUCCESS;
+}
+
+extern "C" int msp_mat_get_value_copy_bytes(const msp_mat* A, int64_t* bytes) {
+  ARGCHK(A && bytes, MSP_ERR_ARG_NULL, "NULL argument");
+  *bytes = A->p32 ? 8 * (A->nnz + 2) : 0;
+  return MSP_SUCCESS;
+}
+
+// W = A~ (sdev[0] x): the scaled MatMult only (stop flag honoured, no vout, no residual mode).  The copy must be
+// current: a call outside a solve builds it here, a solve has built it before its first cycle.
+extern "C" int mspi_spmv_scaled_p32(msp_mat* A, const double* x, const double* sdev, double* y, const int* stop) {
+  int rc = mspi_mat_ensure_p32(A);
+  if (rc) return rc;
+  msp_ctx* c = A->ctx;
+  // spmv_bytes with 8 bytes per entry: the packed words, the row pointers, x read once and y written
+  KTimer kt(c, MSP_KERNEL_SPMV, 8.0 * (double)A->nnz + 4.0 * ((double)A->nrows + 1.0) + 16.0 * (double)A->nrows);
+  KCHK(msk_spmv_p32(A->nrows, A->rowptr, A->p32, x, y, A->lds_cap, sdev, stop, A->plane, c->stream));
   return MSP_SUCCESS;
 }
 

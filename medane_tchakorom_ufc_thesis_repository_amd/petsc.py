@@ -347,6 +347,13 @@ class Mat:
         call("msp_mat_get_diagonal", self.h, d.h)
         return d
 
+    def get_value_copy_bytes(self) -> int:
+        """Device bytes of the single-precision copy of the values that "single" operator-precision solves read:
+        0 until a solve has built it, then 8 (nnz + 2) (msp_mat_get_value_copy_bytes)."""
+        v = C.c_int64()
+        call("msp_mat_get_value_copy_bytes", self.h, C.byref(v))
+        return v.value
+
     STORAGE = {"none": -1, "csr": 0, "dv": 1, "stencil": 2}
 
     def set_storage(self, storage: str):
@@ -779,6 +786,23 @@ class KSP:
         call("msp_ksp_get_basis_precision", self.h, C.byref(v))
         return {n: w for w, n in self.BASIS_PRECISIONS.items()}[v.value]
 
+    # storage precision of the operator's values in the Arnoldi products (msp_ksp_set_operator_precision): "single"
+    # has them read a copy of a CSR-storage operator whose values are floats packed with their columns, 8 bytes per
+    # entry for 12, every row summed in double in the same order; the restart's residual reads the double values
+    OPERATOR_PRECISIONS = {"double": 0, "single": 1}
+
+    def set_operator_precision(self, precision: str):
+        word = str(precision).lower()
+        if word not in self.OPERATOR_PRECISIONS:
+            raise MsplitError(PETSC_ERR_ARG_OUTOFRANGE, f"operator precision {precision!r}: expected one of "
+                                                        f"{sorted(self.OPERATOR_PRECISIONS)}")
+        call("msp_ksp_set_operator_precision", self.h, self.OPERATOR_PRECISIONS[word])
+
+    def get_operator_precision(self) -> str:
+        v = C.c_int()
+        call("msp_ksp_get_operator_precision", self.h, C.byref(v))
+        return {n: w for w, n in self.OPERATOR_PRECISIONS.items()}[v.value]
+
     # preconditioner (msp_ksp_set_pc_type): "jacobi" is PETSc's PCJACOBI (diagonal) on the left with the
     # preconditioned residual norm, KSPGMRES's defaults; double basis and DBR reduction only
     PC_TYPES = {"none": 0, "jacobi": 1}
@@ -856,6 +880,12 @@ class KSP:
                 raise MsplitError(PETSC_ERR_ARG_OUTOFRANGE, f"-{p}msplit_basis_precision {word}: expected one of "
                                                             f"{sorted(self.BASIS_PRECISIONS)}")
             self.set_basis_precision(word)
+        if opts.has("msplit_operator_precision", p):
+            word = opts.get_string("msplit_operator_precision", "double", p)
+            if str(word).lower() not in self.OPERATOR_PRECISIONS:
+                raise MsplitError(PETSC_ERR_ARG_OUTOFRANGE, f"-{p}msplit_operator_precision {word}: expected one of "
+                                                            f"{sorted(self.OPERATOR_PRECISIONS)}")
+            self.set_operator_precision(word)
         if opts.has("pc_type", p):
             self.set_pc_type(pt)
 

@@ -14,6 +14,7 @@ typedef struct {
   PetscReal haptol, breakdowntol;
   PetscInt reduction; /* -msplit_reduction dbr|seq on this KSP's prefix; -1: the shared context's order */
   PetscInt basis_precision; /* -msplit_basis_precision double|single|block16: MSP_BASIS_F64 / _F32 / _B16 */
+  PetscInt operator_precision; /* -msplit_operator_precision double|single: MSP_OPER_F64 / _F32 */
 } KSP_MSplit;
 
 /* -msplit_reduction: the device reduction order (include/msplit.h msp_ctx_set_reduction).  "seq" is
@@ -25,6 +26,11 @@ static const char *const MSplitReductions[] = {"dbr", "seq", "MSplitReduction", 
  * single and block16 exclude -msplit_reduction seq */
 static const char *const MSplitBasisPrecisions[] = {"double",  "single", "block16", "MSplitBasisPrecision",
                                                     "MSPLIT_BASIS_", NULL};
+/* -msplit_operator_precision: the Arnoldi products read the operator's values as stored, or a float copy of a
+ * CSR-storage operator's values packed with their columns, every row summed in double in the same order
+ * (include/msplit.h msp_ksp_set_operator_precision); single excludes -msplit_reduction seq */
+static const char *const MSplitOperatorPrecisions[] = {"double", "single", "MSplitOperatorPrecision",
+                                                       "MSPLIT_OPERATOR_", NULL};
 
 /* -msplit_minimization_precision: the operator R of msplitlsqr stored in HBM as double, or as float with all
  * arithmetic in double (include/msplit.h msp_dense_create_prec); single excludes -msplit_reduction seq */
@@ -238,6 +244,7 @@ static PetscErrorCode KSPSolve_MSplitGMRES_Body(KSP ksp)
   o.guess_nonzero = ksp->guess_zero ? 0 : 1;
   MSPCall(msp_ksp_set_opts(ms->ksp, &o));
   MSPCall(msp_ksp_set_basis_precision(ms->ksp, (int)ms->basis_precision));
+  MSPCall(msp_ksp_set_operator_precision(ms->ksp, (int)ms->operator_precision));
   PetscCall(VecGetLocalSize(ksp->vec_rhs, &n));
   PetscCall(VecGetArrayRead(ksp->vec_rhs, &b));
   MSPCall(msp_vec_set_values(ms->b, 0, n, b));
@@ -276,6 +283,10 @@ static PetscErrorCode KSPSetFromOptions_MSplitGMRES(KSP ksp, PetscOptionItems *P
   PetscCall(PetscOptionsEnum("-msplit_basis_precision", "storage precision of the Krylov basis", NULL,
                              MSplitBasisPrecisions, bp, &bp, NULL));
   ms->basis_precision = (PetscInt)bp;
+  PetscEnum op = (PetscEnum)ms->operator_precision;
+  PetscCall(PetscOptionsEnum("-msplit_operator_precision", "storage precision of the operator's values in the Arnoldi products",
+                             NULL, MSplitOperatorPrecisions, op, &op, NULL));
+  ms->operator_precision = (PetscInt)op;
   PetscCall(PetscOptionsReal("-ksp_gmres_breakdown_tolerance", "restart breakdown tolerance", NULL, ms->breakdowntol,
                              &ms->breakdowntol, NULL));
   PetscOptionsHeadEnd();
