@@ -273,6 +273,16 @@ def gmres(rowptr, col, val, b, x0=None, restart=30, max_it=10000, rtol=1e-5, abs
     return np.array(x), {"its": st["its"], "reason": st["reason"], "rnorm": st["rnorm"], "hist": np.array(hist)}
 
 
+def _div(a, b):
+    """a / b as IEEE 754 has it (x / 0 = +-inf, 0 / 0 = NaN) where Python raises ZeroDivisionError: KSPLSQR divides
+    by alpha and rho without looking, and the NaN it gets is what ends the solve (reason -9)."""
+    if b != 0.0:
+        return a / b
+    if a == 0.0 or math.isnan(a):
+        return math.nan
+    return math.copysign(math.inf, a) * math.copysign(1.0, b)
+
+
 def lsqr(R, b, max_it=10000, rtol=1e-5, abstol=1e-50, divtol=1e4, exact_norm=False, conv_test="lsqr"):
     """KSPSolve_LSQR [PETSc-ext], PCNONE, zero initial guess, sequential sums:
     R is a list of rows (each a list of s floats), b a list.  Returns (x, its,
@@ -354,7 +364,7 @@ def lsqr(R, b, max_it=10000, rtol=1e-5, abstol=1e-50, divtol=1e4, exact_norm=Fal
     u = scale(u, 1.0 / beta)
     v = gemvt(u)
     alpha = nrm(v)
-    v = scale(v, 1.0 / alpha)
+    v = scale(v, _div(1.0, alpha))
     w = list(v)
     if exact_norm:
         acc = 0.0
@@ -383,16 +393,16 @@ def lsqr(R, b, max_it=10000, rtol=1e-5, abstol=1e-50, divtol=1e4, exact_norm=Fal
         if math.isnan(alpha) or math.isinf(alpha):
             reason = -9
             break
-        v1 = scale(v1, 1.0 / alpha)
+        v1 = scale(v1, _div(1.0, alpha))
         rho = math.sqrt(rhobar * rhobar + beta * beta)
-        c, sn = rhobar / rho, beta / rho
+        c, sn = _div(rhobar, rho), _div(beta, rho)
         theta = sn * alpha
         rhobar = -c * alpha
         phi = c * phibar
         phibar = sn * phibar
         tau = sn * phi
-        x = axpy(x, phi / rho, w)
-        w = aypx(w, -theta / rho, v1)
+        x = axpy(x, _div(phi, rho), w)
+        w = aypx(w, _div(-theta, rho), v1)
         arnorm = alpha * abs(tau)
         rnorm = phibar
         its += 1

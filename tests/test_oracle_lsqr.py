@@ -11,7 +11,9 @@ import numpy as np
 import pytest
 import scipy.sparse.linalg as sla
 
+import _lsqr_branch_cases as bc
 import twin
+from guarded import assert_same_bits
 
 RNG = np.random.default_rng(20251121)
 
@@ -34,6 +36,23 @@ def test_lsqr_oracle_equals_twin(oracle, conv, exact):
     assert r["rnorm"] == rnorm
     assert np.array_equal(r["hist"], np.array(hist))
     assert np.array_equal(x, np.array(xt))
+
+
+@pytest.mark.parametrize("name,conv", bc.RUNS)
+def test_lsqr_termination_branches_oracle_equals_twin(oracle, name, conv):
+    """Every termination branch of KSPSolve_LSQR on a crafted input (tests/_lsqr_branch_cases.py: NaN / inf in b
+    or R, R = 0, b orthogonal to range(R), beta == 0, the three tolerances at n = 0 and after a step, the two
+    normal-equation tests, skip, max_it): the C oracle and the pure-Python twin end with the reason the case is
+    named for and agree bit for bit, NaNs included."""
+    R, b, o, want = bc.case(name)
+    x, r = oracle.lsqr(bc.blocks(R, b)[0], bc.blocks(R, b)[1], conv_test=conv, **o)
+    xt, its, reason, rnorm, hist = twin.lsqr(R.tolist(), b.tolist(), conv_test=("default", "lsqr", "skip")[conv],
+                                             **o)
+    assert r["reason"] == want[conv], f"{name} does not reach its branch: reason {r['reason']}"
+    assert (r["its"], r["reason"]) == (its, reason)
+    assert_same_bits(r["rnorm"], rnorm, "rnorm")
+    assert_same_bits(r["hist"], np.array(hist), "history")
+    assert_same_bits(x, np.array(xt), "x")
 
 
 def test_lsqr_multiblock_seq_is_the_global_sequential_order(oracle):
