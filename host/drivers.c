@@ -202,6 +202,19 @@ static int ksp_from_options(msp_ksp *k, const msd_options *o, const char *p, msp
     }
   }
   CK(msp_ksp_set_pc_type(k, jacobi ? MSP_PC_JACOBI : MSP_PC_NONE));
+  /* -<prefix>ksp_gmres_cgs_refinement_type refine_never|refine_ifneeded|refine_always: a second Gram-Schmidt pass,
+   * decided on the device (msp_ksp_set_cgs_refinement) */
+  const char *rt = msd_opt_str(o, p, "ksp_gmres_cgs_refinement_type", NULL);
+  if (rt) {
+    if (!strcasecmp(rt, "refine_never")) CK(msp_ksp_set_cgs_refinement(k, MSP_CGS_REFINE_NEVER));
+    else if (!strcasecmp(rt, "refine_ifneeded")) CK(msp_ksp_set_cgs_refinement(k, MSP_CGS_REFINE_IFNEEDED));
+    else if (!strcasecmp(rt, "refine_always")) CK(msp_ksp_set_cgs_refinement(k, MSP_CGS_REFINE_ALWAYS));
+    else {
+      fprintf(stderr, "-%sksp_gmres_cgs_refinement_type %s: expected refine_never, refine_ifneeded or refine_always\n",
+              p, rt);
+      return MSP_ERR_ARG_OUTOFRANGE;
+    }
+  }
   CK(msp_ksp_get_opts(k, ko));
   ko->restart = (int32_t)msd_opt_int(o, p, "ksp_gmres_restart", ko->restart);
   ko->max_it = (int32_t)msd_opt_int(o, p, "ksp_max_it", ko->max_it);

@@ -48,7 +48,8 @@ static int usage(void) {
                   "asynchronous-multisplitting-asynchronous-minimization-global> "
                   "-m M -n N [-s S] [-rtol R] [-dim 3 -p P] [-peclet px,py,pz] [-nb B] [-msplit_reduction dbr|seq] [-msplit_minimization lsqr|rtr] "
                   "[-msplit_minimization_precision double|single] [-innerK_msplit_basis_precision double|single|block16] "
-                  "[-innerK_pc_type none|jacobi] [-innerK_msplit_operator_precision double|single] [-json] ...\n");
+                  "[-innerK_pc_type none|jacobi] [-innerK_msplit_operator_precision double|single] "
+                  "[-innerK_ksp_gmres_cgs_refinement_type refine_never|refine_ifneeded|refine_always] [-json] ...\n");
   return 2;
 }
 

@@ -289,6 +289,7 @@ typedef struct msp_ksp_opts {
 
 int msp_ksp_get_default_opts(msp_ksp_opts *o);
 /* KSPCreate + KSPSetType(KSPGMRES) + PCNONE (msp_ksp_set_pc_type: left PCJACOBI), CGS with REFINE_NEVER
+ * (msp_ksp_set_cgs_refinement: refine_ifneeded / refine_always)
  * (initializeKSP, utils.c:512-541; canonical options running_bulk_test_g5k:64-70). */
 int msp_ksp_create(msp_ctx *ctx, msp_ksp **ksp);
 int msp_ksp_destroy(msp_ksp **ksp);
@@ -335,7 +336,8 @@ int msp_ksp_get_residual_history(const msp_ksp *ksp, const double **hist, int32_
 int msp_ksp_set_basis_precision(msp_ksp *ksp, int prec);
 int msp_ksp_get_basis_precision(const msp_ksp *ksp, int *prec);
 /* Device bytes the KSP holds once set up and solved with: the basis, W / the current vector, the recurrence
- * block, and under MSP_PC_JACOBI the n doubles of the inverse diagonal (0 before set-up). */
+ * block (with the CGS refinement's block behind it), and under MSP_PC_JACOBI the n doubles of the inverse diagonal
+ * (0 before set-up). */
 int msp_ksp_get_work_bytes(const msp_ksp *ksp, int64_t *bytes);
 /* Preconditioner (-pc_type none|jacobi).
  * MSP_PC_NONE (default): PCNONE.
@@ -389,6 +391,32 @@ int msp_ksp_get_pc_type(const msp_ksp *ksp, int *pc_type);
 #define MSP_OPER_F32 1
 int msp_ksp_set_operator_precision(msp_ksp *ksp, int prec);
 int msp_ksp_get_operator_precision(const msp_ksp *ksp, int *prec);
+/* Iterative refinement of the classical Gram-Schmidt step (-ksp_gmres_cgs_refinement_type refine_never|
+ * refine_ifneeded|refine_always; KSPGMRESSetCGSRefinementType / KSPGMRESGetCGSRefinementType).  The step is PETSc
+ * 3.22.1's KSPGMRESClassicalGramSchmidtOrthogonalization.  With v_j the normalised basis and W = A v_it:
+ *   pass 1   h_j = W . v_j (VecMDot), u = W - sum h_j v_j (VecMAXPY), ss1 = ||u||^2;
+ *   decision MSP_CGS_REFINE_NEVER (default): none.  MSP_CGS_REFINE_ALWAYS: refine.  MSP_CGS_REFINE_IFNEEDED: refine
+ *            when sqrt(ss1) < sqrt(sum_j h_j h_j), the sum taken in j order from 0.0 -- the first pass cancelled more
+ *            than it kept.  A non-finite sqrt(ss1) there ends the solve with MSP_DIVERGED_NANORINF, as a non-finite
+ *            dot does (KSPCheckNorm / KSPCheckDot inside the orthogonalisation);
+ *   pass 2   c_j = u . v_j, u' = u - sum c_j v_j, ss2 = ||u'||^2;
+ *   column   hh_j = 0.0; hh_j -= -h_j; on a refined step hh_j -= -c_j; the new vector's norm is sqrt(ss2) on a
+ *            refined step and sqrt(ss1) otherwise.
+ * The decision is taken on the device, so a captured restart cycle needs no host round trip.  REFINE_NEVER is the
+ * solve as it was: same launches, same bits.  With refinement the step stores W (no W-free or operator-fused
+ * step); pass 1 and pass 2's VecMDot are one sweep over the basis, so refine_ifneeded costs nothing on a step that
+ * does not refine and one more sweep on one that does.  Composes with MSP_OPER_F32.  A solve returns MSP_ERR_SUP,
+ * naming the cause, with MSP_BASIS_F32 / MSP_BASIS_B16 (pass 2 runs before the store's rounding and cannot repair
+ * it), with MSP_PC_JACOBI, and on a context in MSP_REDUCE_SEQ.  Changing the type drops the captured cycles.  Any
+ * other value: MSP_ERR_ARG_OUTOFRANGE. */
+#define MSP_CGS_REFINE_NEVER 0
+#define MSP_CGS_REFINE_IFNEEDED 1
+#define MSP_CGS_REFINE_ALWAYS 2
+int msp_ksp_set_cgs_refinement(msp_ksp *ksp, int type);       /* KSPGMRESSetCGSRefinementType */
+int msp_ksp_get_cgs_refinement(const msp_ksp *ksp, int *type); /* KSPGMRESGetCGSRefinementType */
+/* Arnoldi steps of the last solve that ran pass 2 (0 under REFINE_NEVER): what PETSc reports through PetscInfo
+ * ("Refining classical Gram-Schmidt"), KSPGMRESClassicalGramSchmidtOrthogonalization. */
+int msp_ksp_get_cgs_refinement_count(const msp_ksp *ksp, int32_t *n);
 
 /* ------------------------------------------------------------------ dense */
 /* A block of rows of a MATDENSE / MATMPIDENSE matrix, column-major in HBM with

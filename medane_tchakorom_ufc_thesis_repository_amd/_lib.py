@@ -114,6 +114,9 @@ _SIGS = {
     "msp_mat_get_diagonal": [_vp, _vp],
     "msp_ksp_set_operator_precision": [_vp, C.c_int],
     "msp_ksp_get_operator_precision": [_vp, _P(C.c_int)],
+    "msp_ksp_set_cgs_refinement": [_vp, C.c_int],
+    "msp_ksp_get_cgs_refinement": [_vp, _P(C.c_int)],
+    "msp_ksp_get_cgs_refinement_count": [_vp, _i32p],
     "msp_mat_get_value_copy_bytes": [_vp, _P(C.c_int64)],
     "msp_mat_create_box_stencil_ext": [_vp, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                        _P(_vp)],

@@ -2,7 +2,8 @@
  * ksp_gmres.c -- KSPGMRES host logic over device-resident Krylov vectors.
  *
  * Restates PETSc 3.22.1's KSPSolve_GMRES / KSPGMRESCycle / classical
- * Gram-Schmidt (KSP_GMRES_CGS_REFINE_NEVER: one pass, no refinement) / KSPGMRESUpdateHessenberg / KSPGMRESBuildSoln /
+ * Gram-Schmidt (KSP_GMRES_CGS_REFINE_NEVER, one pass, by default; msp_ksp_set_cgs_refinement: REFINE_IFNEEDED and
+ * REFINE_ALWAYS, a second pass decided on the device) / KSPGMRESUpdateHessenberg / KSPGMRESBuildSoln /
  * KSPConvergedDefault with PCNONE -- the inner solve the reference calls from
  * inner_solver() (src/utils/utils.c:950-970) and gmres_solution.c:70.
  *
@@ -61,6 +62,15 @@
  *            residual correction at each restart.  Inside one cycle the recurrence residual is the rounded
  *            operator's and can differ from the true one by about 2^-24 || |A| |dx| ||; from a zero guess within
  *            one cycle, x solves the rounded system.
+ *   refined  MSP_CGS_REFINE_IFNEEDED / _ALWAYS (msp_ksp_set_cgs_refinement) on the f64 basis without Jacobi: a
+ *            stored-W step of five launches, the same on every step so that a captured cycle replays it: MatMult
+ *            (fused with MDot where the operator allows; the packed copy's under MSP_OPER_F32), pass 1 fused with
+ *            pass 2's MDot stage 1 (k_maxpy_mdot: u = W - sum h_j v_j stored to VV(it+1), the partials of ||u||^2 and
+ *            of every c_j = u . v_j, one sweep), the decide kernel (folds them; refine and skip), pass 2's MAXPY in
+ *            place on VV(it+1) (k_maxpy_chunk, returning at once on skip), the update kernel (column h + c, tt from
+ *            ss2 or ss1, then k_norm_update's statements).  Steps with it + 2 > MSPI_MAX_GROUP take
+ *            mspi_maxpy_norm_basis then mspi_mdot_basis instead of the fused pass: the same bits.  Neither opfuse
+ *            nor wfree (a W-free refined step is not built).
  *
  * Data layout: VV(0..min(m, max_it)) are one allocation of (min(m, max_it)+1) x stride elements; stride = n rounded
  * up to 512 doubles, to 1024 floats or to 2048 int16 (4 KiB each way); block16 keeps its int32 exponents,
@@ -107,6 +117,9 @@ struct msp_ksp {
   double *dinv;             /* device, Jacobi: n doubles, 1 / a_ii by PCSetUp's rule */
   int dinv_valid;           /* dinv holds the current operator's (reset by msp_ksp_set_operators) */
   int oper_prec;            /* MSP_OPER_F64 / MSP_OPER_F32: what the Arnoldi MatMult reads */
+  int cgs;                  /* MSP_CGS_REFINE_NEVER / _IFNEEDED / _ALWAYS */
+  mspi_gmres_refine *rf;    /* device: the refinement's block, behind the recurrence arrays in gblock */
+  int nrefine;              /* steps of the last solve that ran pass 2 */
   size_t basis_bytes, gblock_bytes, vec_bytes; /* sizes of the allocations (vec_bytes: tmp and cur, each) */
   mspi_gmres_dev g;         /* device-resident recurrence state and arrays */
   void *gblock;             /* the single device allocation behind g */
@@ -173,6 +186,7 @@ static void ksp_free_work(msp_ksp *k) {
   k->expo = NULL;
   k->basis_bytes = k->gblock_bytes = k->vec_bytes = 0;
   k->gblock = NULL;
+  k->rf = NULL;
   k->hst = NULL;
   k->hist = NULL;
   memset(&k->g, 0, sizeof(k->g));
@@ -316,6 +330,43 @@ int msp_ksp_get_operator_precision(const msp_ksp *k, int *prec) {
   return MSP_SUCCESS;
 }
 
+int msp_ksp_set_cgs_refinement(msp_ksp *k, int type) {
+  if (!k) {
+    mspi_set_error(MSP_ERR_ARG_NULL, "NULL argument");
+    return MSP_ERR_ARG_NULL;
+  }
+  if (type != MSP_CGS_REFINE_NEVER && type != MSP_CGS_REFINE_IFNEEDED && type != MSP_CGS_REFINE_ALWAYS) {
+    mspi_set_error(MSP_ERR_ARG_OUTOFRANGE,
+                   "CGS refinement %d is none of MSP_CGS_REFINE_NEVER, MSP_CGS_REFINE_IFNEEDED, MSP_CGS_REFINE_ALWAYS",
+                   type);
+    return MSP_ERR_ARG_OUTOFRANGE;
+  }
+  if (type != k->cgs) { /* other launches in every captured cycle; the work vectors stay */
+    msp_ctx_synchronize(k->ctx);
+    ksp_drop_graphs(k);
+  }
+  k->cgs = type;
+  return MSP_SUCCESS;
+}
+
+int msp_ksp_get_cgs_refinement(const msp_ksp *k, int *type) {
+  if (!k || !type) {
+    mspi_set_error(MSP_ERR_ARG_NULL, "NULL argument");
+    return MSP_ERR_ARG_NULL;
+  }
+  *type = k->cgs;
+  return MSP_SUCCESS;
+}
+
+int msp_ksp_get_cgs_refinement_count(const msp_ksp *k, int32_t *n) {
+  if (!k || !n) {
+    mspi_set_error(MSP_ERR_ARG_NULL, "NULL argument");
+    return MSP_ERR_ARG_NULL;
+  }
+  *n = k->nrefine;
+  return MSP_SUCCESS;
+}
+
 int msp_ksp_get_work_bytes(const msp_ksp *k, int64_t *bytes) {
   if (!k || !bytes) {
     mspi_set_error(MSP_ERR_ARG_NULL, "NULL argument");
@@ -361,7 +412,8 @@ int msp_ksp_set_up(msp_ksp *k) {
   const size_t vv_bytes = (size_t)mv * (size_t)k->stride * elem;
   k->nchunks = (k->n + MSPI_DBR_CHUNK - 1) / MSPI_DBR_CHUNK;
   k->basis_bytes = vv_bytes + (b16 ? (size_t)mv * (size_t)k->nchunks * sizeof(int32_t) : 0) + 4096;
-  k->gblock_bytes = st_bytes + nd * sizeof(double);
+  /* the CGS refinement's block (mode, refine, skip, count, ss1, ss2, c(0..m+1)) behind the arrays */
+  k->gblock_bytes = st_bytes + nd * sizeof(double) + MSPI_REFINE_BYTES(m);
   k->vec_bytes = (size_t)((k->n + 511) / 512 * 512) * sizeof(double) + 4096;
   int rc = mspi_malloc(k->ctx, (void **)&k->basis, k->basis_bytes);
   /* W (k->tmp) is allocated by the first cycle that stores it (ensure_w): the W-free step never does */
@@ -392,6 +444,7 @@ int msp_ksp_set_up(msp_ksp *k) {
   k->g.sc = d;
   d += m + 2;
   k->g.hist = d;
+  k->rf = (mspi_gmres_refine *)(d + k->hist_cap);
   k->setup = 1;
   if ((rc = pc_set_up(k))) ksp_free_work(k);
   return rc;
@@ -416,6 +469,10 @@ static void step_kind(const msp_ksp *k, int *opfuse, int *wfree) {
     return;
   }
   if (k->pc_type == MSP_PC_JACOBI) { /* w = dinv .* W is formed by the CGS kernels from the stored W */
+    *opfuse = *wfree = 0;
+    return;
+  }
+  if (k->cgs != MSP_CGS_REFINE_NEVER) { /* the refined step reads a stored W; a W-free one is not built */
     *opfuse = *wfree = 0;
     return;
   }
@@ -517,7 +574,32 @@ static int enqueue_cycle(msp_ksp *k, double *x, int K) {
       rc = mspi_maxpy_norm_update_march(k->A, VV(k, it), sc + it, VV(k, it + 1), it + 1, k->basis, k->stride, sc,
                                         k->g, k->o.restart, stop);
   }
-  for (int it = 0; it < K && !rc && !opfuse && !wfree; ++it) {
+  for (int it = 0; it < K && !rc && k->cgs != MSP_CGS_REFINE_NEVER; ++it) {
+    /* the refined step: MatMult (+ MDot), pass 1 (+ pass 2's MDot), decide, pass 2's MAXPY, update -- the same five
+     * launches whatever the device decides (a step that does not refine returns from the fourth on rf->skip) */
+    const int nv = it + 1;
+    rc = k->oper_prec == MSP_OPER_F32 ? MSP_ERR_SUP /* the fused kernel reads the f64 values */
+                                      : mspi_spmv_mdot(k->A, VV(k, it), sc + it, k->tmp, nv, k->basis, k->stride, sc,
+                                                       k->g.h, stop);
+    if (rc == MSP_ERR_SUP) {
+      rc = step_matmult(k, VV(k, it), sc + it, stop);
+      if (!rc) rc = mspi_mdot_basis(c, k->tmp, nv, k->basis, k->stride, sc, k->n, k->g.h, stop);
+    }
+    if (!rc && mspi_gm_refine_fused(nv)) {
+      rc = mspi_maxpy_norm_mdot_basis(c, k->tmp, VV(k, it + 1), nv, k->basis, k->stride, sc, k->n, k->g.h, NULL, NULL,
+                                      stop);
+      if (!rc) rc = mspi_gm_refine_decide(c, k->g, k->rf, mspi_ctx_partial(c), k->nchunks);
+    } else if (!rc) { /* more rows than the partial buffer holds: the two kernels the fused one restates */
+      rc = mspi_maxpy_norm_basis(c, k->tmp, VV(k, it + 1), nv, k->basis, k->stride, sc, k->n, k->g.h, &k->rf->ss1,
+                                 stop);
+      if (!rc)
+        rc = mspi_mdot_basis(c, VV(k, it + 1), nv, k->basis, k->stride, sc, k->n, MSPI_REFINE_C(k->rf), stop);
+      if (!rc) rc = mspi_gm_refine_decide(c, k->g, k->rf, NULL, k->nchunks);
+    }
+    if (!rc) rc = mspi_gm_refine_maxpy2(c, VV(k, it + 1), nv, k->basis, k->stride, sc, k->n, k->rf);
+    if (!rc) rc = mspi_gm_refine_update(c, k->g, k->rf, mspi_ctx_partial(c), k->nchunks, (int)k->o.restart);
+  }
+  for (int it = 0; it < K && !rc && !opfuse && !wfree && k->cgs == MSP_CGS_REFINE_NEVER; ++it) {
     /* W = A (sc[it] VV(it))  (KSP_PCApplyBAorAB with PCNONE on the normalised VV(it)),
      * CGS: h = VecMDot(W, VV(0..it)) -- one fused launch where the operator allows */
     rc = k->oper_prec == MSP_OPER_F32 ? MSP_ERR_SUP /* the fused kernel reads the f64 values */
@@ -622,6 +704,23 @@ int msp_ksp_solve(msp_ksp *k, const msp_vec *b, msp_vec *x) {
                                 "for bit, which a rounded operator cannot");
     return MSP_ERR_SUP;
   }
+  if (k->cgs != MSP_CGS_REFINE_NEVER) {
+    const char *w = k->cgs == MSP_CGS_REFINE_ALWAYS ? "MSP_CGS_REFINE_ALWAYS" : "MSP_CGS_REFINE_IFNEEDED";
+    if (compressed(k)) {
+      mspi_set_error(MSP_ERR_SUP, "%s is built for the double basis only, not %s: the second pass runs before the "
+                                  "store's rounding and cannot repair it",
+                     w, k->basis_prec == MSP_BASIS_B16 ? "MSP_BASIS_B16" : "MSP_BASIS_F32");
+      return MSP_ERR_SUP;
+    }
+    if (k->pc_type == MSP_PC_JACOBI) {
+      mspi_set_error(MSP_ERR_SUP, "%s is not built with MSP_PC_JACOBI: its fused kernels have no second pass", w);
+      return MSP_ERR_SUP;
+    }
+    if (mspi_reduce_seq(k->ctx)) {
+      mspi_set_error(MSP_ERR_SUP, "%s needs the DBR reduction: its fused kernel has no MSP_REDUCE_SEQ form", w);
+      return MSP_ERR_SUP;
+    }
+  }
   int rc = mspi_set_device(k->ctx);
   /* the packed copy, built or rebuilt before any capture; an operator whose products do not read its CSR arrays
    * and values beyond the float range are refused here, before any work is allocated */
@@ -657,6 +756,12 @@ int msp_ksp_solve(msp_ksp *k, const msp_vec *b, msp_vec *x) {
     h->bnorm = sqrt(bb);
   }
   if ((rc = mspi_h2d_async(c, k->g.st, h, sizeof(*h)))) return rc;
+  k->nrefine = 0;
+  if (k->cgs != MSP_CGS_REFINE_NEVER) { /* skip = 1 outside a step's decide..update window */
+    const mspi_gmres_refine r0 = {k->cgs, 0, 1, 0, 0.0, 0.0};
+    if ((rc = mspi_h2d_sync(c, k->rf, &r0, sizeof(r0)))) return rc;
+    if ((rc = mspi_reserve_partial(c, k->n))) return rc; /* the cycle hands the buffer's address to its kernels */
+  }
   if (guess_zero && (rc = mspi_set(c, x->d, k->n, 0.0))) return rc; /* KSPSolve zeroes x */
 
   int cycle_zero_guess = guess_zero, itcount = 0, its = 0, reason = 0;
@@ -685,6 +790,11 @@ int msp_ksp_solve(msp_ksp *k, const msp_vec *b, msp_vec *x) {
   k->rnorm = h->rnorm;
   k->nhist = h->nhist < k->hist_cap ? h->nhist : k->hist_cap;
   if (k->nhist && (rc = mspi_d2h_sync(c, k->hist, k->g.hist, (size_t)k->nhist * sizeof(double)))) return rc;
+  if (k->cgs != MSP_CGS_REFINE_NEVER) {
+    mspi_gmres_refine r1;
+    if ((rc = mspi_d2h_sync(c, &r1, k->rf, sizeof(r1)))) return rc;
+    k->nrefine = r1.count;
+  }
   return MSP_SUCCESS;
 }
 

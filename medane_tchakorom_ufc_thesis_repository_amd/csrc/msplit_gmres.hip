@@ -305,6 +305,174 @@ __global__ __launch_bounds__(kUT) void k_norm_update(mspi_gmres_dev g, const dou
   if (t < kStW) const_cast<int32_t*>(reinterpret_cast<const int32_t*>(g.st))[t] = reinterpret_cast<int32_t*>(&lst)[t];
 }
 
+// ---- CGS iterative refinement (KSPGMRESClassicalGramSchmidtOrthogonalization with refine_ifneeded / refine_always)
+// The decision after pass 1, on the device.  With partial != nullptr the fused pass left stage-1 partials: row
+// it + 1 is ||u||^2 (folded in fold_partials' order), rows 0..it are c_j = u . v_j (k_dot_stage2's order, which is
+// the same one); otherwise ss1 and c are already in the block.  always: refine.  ifneeded: refine when
+// ||u|| < ||h||, hnrm summed in j order from 0.0; a non-finite ||u|| is KSPCheckNorm (the update kernel ends the
+// cycle on it), as is a non-finite h_j (KSPCheckDot): neither refines.
+__global__ __launch_bounds__(kUT) void k_refine_decide(mspi_gmres_dev g, mspi_gmres_refine* rf,
+                                                       const double* __restrict__ partial, int64_t nchunks) {
+  __shared__ double red[2][4];
+  const mspi_gmres_state* st = g.st;
+  if (st->stop) return;  // uniform
+  const int it = st->it, t = threadIdx.x;
+  double* c = MSPI_REFINE_C(rf);
+  double ss1 = 0.0;
+  if (partial) {
+    for (int r = 0; r <= it + 1; ++r) {  // red is double-buffered: one barrier per row
+      const double s = fold_partials(partial + (int64_t)r * nchunks, nchunks, red[r & 1]);
+      if (r <= it) {
+        if (t == 0) c[r] = s;
+      } else {
+        ss1 = s;
+      }
+    }
+  } else {
+    ss1 = rf->ss1;
+  }
+  if (t != 0) return;
+  rf->ss1 = ss1;
+  int refine = 0;
+  bool nan_dot = false;
+  for (int j = 0; j <= it; ++j)
+    if (bad(g.h[j])) nan_dot = true;
+  if (!nan_dot) {
+    if (rf->mode == MSP_CGS_REFINE_ALWAYS) {
+      refine = 1;
+    } else if (rf->mode == MSP_CGS_REFINE_IFNEEDED) {
+      double hsq = 0.0;
+      for (int j = 0; j <= it; ++j) hsq = hsq + g.h[j] * g.h[j];
+      const double hnrm = sqrt(hsq), wnrm = sqrt(ss1);
+      if (!bad(wnrm) && wnrm < hnrm) refine = 1;
+    }
+  }
+  rf->refine = refine;
+  rf->skip = !refine;
+  if (refine) rf->count++;
+}
+
+// k_norm_update with the column and tt of a refined step: hh_j = 0.0; hh_j -= -h_j; on a refined step also
+// hh_j -= -c_j, and tt = sqrt(refine ? ss2 : ss1), ss2 folded from the partials pass 2's MAXPY left.  KSPCheckDot
+// on h, KSPCheckNorm on ||u|| (ifneeded) and KSPCheckDot on c (refined) all take k_norm_update's nan_dot branch.
+// Everything after tt is k_norm_update's statements.
+__global__ __launch_bounds__(kUT) void k_refine_update(mspi_gmres_dev g, mspi_gmres_refine* rf,
+                                                       const double* __restrict__ partial, int64_t nchunks, int m) {
+  __shared__ double red[4];
+  __shared__ mspi_gmres_state lst;
+  extern __shared__ double lds[];  // hh column, cc, ss, grs, c: m+2 each
+  const int t = threadIdx.x, m2 = m + 2;
+  double* lh = lds;
+  double* lc = lds + m2;
+  double* ls = lds + 2 * m2;
+  double* lg = lds + 3 * m2;
+  double* lr = lds + 4 * m2;
+  const double* cdev = MSPI_REFINE_C(rf);
+  if (t < kStW) reinterpret_cast<int32_t*>(&lst)[t] = reinterpret_cast<const int32_t*>(g.st)[t];
+  for (int j = t; j < m2; j += kUT) {
+    lh[j] = g.h[j];
+    lc[j] = g.cc[j];
+    ls[j] = g.ss[j];
+    lg[j] = g.grs[j];
+    lr[j] = cdev[j];
+  }
+  const int refine = rf->refine, mode = rf->mode;  // uniform
+  double sumsq = rf->ss1;
+  if (refine) sumsq = fold_partials(partial, nchunks, red);  // its barrier publishes the LDS copies too
+  else __syncthreads();
+  if (lst.stop) return;  // uniform
+  mspi_gmres_dev gl = g;
+  gl.st = &lst;  // converged() and log_res() on the LDS state
+  mspi_gmres_state* st = &lst;
+  const int it = st->it;
+  __shared__ int ncol;
+  if (t == 0) {
+    if (refine) rf->ss2 = sumsq;
+    rf->skip = 1;
+    g.h[it + 1] = sumsq;
+    ncol = 0;
+    bool nan_dot = false;
+    for (int j = 0; j <= it; ++j)
+      if (bad(lh[j]) || (refine && bad(lr[j]))) nan_dot = true;
+    if (mode == MSP_CGS_REFINE_IFNEEDED && bad(sqrt(rf->ss1))) nan_dot = true;
+    double* hh = lh;  // the column, built in LDS: hh[j] = 0 - (-h[j]) - (-c[j])
+    double res = st->res;
+    int hapend = 0;
+    bool done = false;
+    if (nan_dot) {
+      st->reason = MSP_DIVERGED_NANORINF;
+      for (int j = 0; j <= it; ++j) hh[j] = 0.0;
+      ncol = it + 1;
+    } else {
+      for (int j = 0; j <= it; ++j) {
+        double v = 0.0;
+        v -= -hh[j];
+        if (refine) v -= -lr[j];
+        hh[j] = v;
+      }
+      const double tt = sqrt(sumsq);
+      if (bad(tt)) {
+        st->reason = MSP_DIVERGED_NANORINF;
+        st->stop = st->skip_build = 1;
+        ncol = it + 1;
+        done = true;
+      } else {
+        st->scale = (tt != 0.0) ? 1.0 / tt : 1.0;  // VecNormalize of VV(it+1), deferred to its readers
+        g.sc[it + 1] = st->scale;
+        hh[it + 1] = tt;
+        double hapbnd = fabs(tt / lg[it]);
+        if (hapbnd > st->haptol) hapbnd = st->haptol;
+        if (tt < hapbnd) hapend = 1;
+        // KSPGMRESUpdateHessenberg on the LDS column
+        for (int j = 1; j <= it; ++j) {
+          const double a = hh[j - 1];
+          hh[j - 1] = lc[j - 1] * a + ls[j - 1] * hh[j];
+          hh[j] = lc[j - 1] * hh[j] - (ls[j - 1] * a);
+        }
+        if (!hapend) {
+          const double r = sqrt(hh[it] * hh[it] + hh[it + 1] * hh[it + 1]);
+          if (r == 0.0) {
+            st->reason = MSP_DIVERGED_NULL;
+          } else {
+            const double c = hh[it] / r, sn = hh[it + 1] / r;
+            g.cc[it] = c;
+            g.ss[it] = sn;
+            const double grs = lg[it];
+            g.grs[it + 1] = -(sn * grs);
+            g.grs[it] = c * grs;
+            hh[it] = c * hh[it] + sn * hh[it + 1];
+            res = fabs(-(sn * grs));
+          }
+        } else {
+          res = 0.0;
+        }
+        ncol = it + 2;
+        st->it = it + 1;
+        st->its++;
+        st->rnorm = res;
+        st->res = res;
+        if (!st->reason) {
+          converged(gl, st->its, res);
+          if (hapend && !st->reason) st->reason = MSP_DIVERGED_BREAKDOWN;
+        }
+      }
+    }
+    if (!done) {
+      const int itn = st->it;
+      if (!st->reason && itn < st->m && st->its < st->max_it) {
+        log_res(gl, res);
+      } else {
+        st->stop = 1;
+        if (itn && (st->reason || st->its >= st->max_it)) log_res(gl, res);
+      }
+    }
+  }
+  __syncthreads();
+  double* col = &HHD(0, it);
+  for (int j = t; j < ncol; j += kUT) col[j] = lh[j];
+  if (t < kStW) const_cast<int32_t*>(reinterpret_cast<const int32_t*>(g.st))[t] = reinterpret_cast<int32_t*>(&lst)[t];
+}
+
 // KSPGMRESBuildSoln(GRS(0), x, x, ksp, it - 1): back-solve in place (nrs
 // aliases GRS); the x update is the accumulate-MAXPY that follows.
 __global__ void k_build(mspi_gmres_dev g) {
@@ -416,6 +584,29 @@ extern "C" int mspi_gm_norm_update(msp_ctx* ctx, mspi_gmres_dev g, const double*
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     mspi_set_error(MSP_ERR_LIB, "k_norm_update: %s", hipGetErrorString(e));
+    return MSP_ERR_LIB;
+  }
+  return MSP_SUCCESS;
+}
+
+extern "C" int mspi_gm_refine_decide(msp_ctx* ctx, mspi_gmres_dev g, mspi_gmres_refine* rf, const double* partial,
+                                     int64_t nchunks) {
+  k_refine_decide<<<1, kUT, 0, mspi_stream(ctx)>>>(g, rf, partial, nchunks);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    mspi_set_error(MSP_ERR_LIB, "k_refine_decide: %s", hipGetErrorString(e));
+    return MSP_ERR_LIB;
+  }
+  return MSP_SUCCESS;
+}
+
+extern "C" int mspi_gm_refine_update(msp_ctx* ctx, mspi_gmres_dev g, mspi_gmres_refine* rf, const double* partial,
+                                     int64_t nchunks, int m) {
+  const size_t lds = (size_t)5 * (m + 2) * sizeof(double);
+  k_refine_update<<<1, kUT, lds, mspi_stream(ctx)>>>(g, rf, partial, nchunks, m);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    mspi_set_error(MSP_ERR_LIB, "k_refine_update: %s", hipGetErrorString(e));
     return MSP_ERR_LIB;
   }
   return MSP_SUCCESS;

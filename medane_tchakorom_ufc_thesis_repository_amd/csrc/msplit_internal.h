@@ -177,6 +177,46 @@ int mspi_maxpy_norm_basis(msp_ctx *ctx, const double *win, double *wout, int nv,
 int mspi_maxpy_accum_basis(msp_ctx *ctx, double *x, const int *nvdev, const double *base, int64_t stride,
                            const double *scale, int64_t n, const double *coef_dev, int nv_expected);
 int mspi_h2d_async(msp_ctx *ctx, void *dev, const void *host, size_t bytes);
+/* ---- CGS iterative refinement (MSP_CGS_REFINE_IFNEEDED / _ALWAYS): a second Gram-Schmidt pass decided on the
+   device.  The block lives behind the recurrence arrays in the KSP's device block (mspi_gmres_state and
+   mspi_gmres_dev are unchanged); c follows the header, m + 2 doubles. ---- */
+typedef struct {
+  int32_t mode;   /* MSP_CGS_REFINE_* */
+  int32_t refine; /* this step runs pass 2 (written by the decide kernel) */
+  int32_t skip;   /* stop || !refine: the flag pass 2's MAXPY returns on; 1 outside a step's decide..update window */
+  int32_t count;  /* steps of this solve that ran pass 2 */
+  double ss1;     /* ||u||^2 after pass 1 */
+  double ss2;     /* ||u'||^2 after pass 2 (written by the update kernel on a refined step) */
+} mspi_gmres_refine;
+/* c(0..it) = u . v_j: the m + 2 doubles behind the header */
+#define MSPI_REFINE_C(rf) ((double *)((rf) + 1))
+#define MSPI_REFINE_BYTES(m) (sizeof(mspi_gmres_refine) + (size_t)((m) + 2) * sizeof(double))
+/* Pass 1 fused with pass 2's MDot stage 1 (k_maxpy_mdot): wout = win - sum_j alpha_j scale_j VV(j), then the DBR
+   partials of wout . scale_v VV(v) in rows 0..nv-1 and of ||wout||^2 in row nv of the context's partial buffer: bit
+   for bit mspi_maxpy_norm_basis followed by mspi_mdot_basis on wout.  c_dev != NULL: the rows are folded here
+   (stage 2) into c_dev[0..nv-1] and sumsq_dev[0]; NULL: left for mspi_gm_refine_decide.  nv + 1 <= MSPI_MAX_GROUP
+   and the DBR reduction, else MSP_ERR_SUP. */
+int mspi_maxpy_norm_mdot_basis(msp_ctx *ctx, const double *win, double *wout, int nv, const double *base,
+                               int64_t stride, const double *scale, int64_t n, const double *alpha_dev, double *c_dev,
+                               double *sumsq_dev, const int *stop);
+/* 1 when a refined step of nv vectors takes the fused kernel (nv + 1 <= MSPI_MAX_GROUP and MSPLIT_GM_REFINE_FUSED
+   not 0) */
+int mspi_gm_refine_fused(int nv);
+/* The decision of step it = st->it (one workgroup).  partial != NULL: rows 0..it and row it + 1 of the fused pass'
+   partials are folded into rf->c and rf->ss1 first (stage 2's order); NULL: both are already there.  Then refine,
+   skip and count.  A no-op when st->stop is set. */
+int mspi_gm_refine_decide(msp_ctx *ctx, mspi_gmres_dev g, mspi_gmres_refine *rf, const double *partial,
+                          int64_t nchunks);
+/* Pass 2's MAXPY in place, w = w - sum_j c_j scale_j VV(j) with the ||w||^2 partials (k_maxpy_chunk unchanged),
+   returning at once when rf->skip is set */
+int mspi_gm_refine_maxpy2(msp_ctx *ctx, double *w, int nv, const double *base, int64_t stride, const double *scale,
+                          int64_t n, const mspi_gmres_refine *rf);
+/* mspi_gm_norm_update with the column h + c and tt = sqrt(refine ? ss2 : ss1); ss2 folded from partial on a refined
+   step.  Leaves rf->skip = 1. */
+int mspi_gm_refine_update(msp_ctx *ctx, mspi_gmres_dev g, mspi_gmres_refine *rf, const double *partial,
+                          int64_t nchunks, int m);
+/* the context's DBR partial buffer (valid after mspi_reserve_partial; enqueued work points at it) */
+const double *mspi_ctx_partial(msp_ctx *ctx);
 /* ---- MSP_BASIS_F32: the same steps over a basis stored as float (msplit_cb.hip), VV(j) = base + j*stride with its
    value (double)VV(j)[i] * scale[j]; all arithmetic f64, DBR only.  rnd(v) = (double)(float)v. ---- */
 /* cur = rnd(r) (f64; may be r itself), v0 = the same as float, sumsq_dev[0] = sum rnd(r)^2 */

@@ -105,6 +105,12 @@ int msk_seq_stage1(const double* w, const Vecs* V, int nv, int64_t n, int self, 
 int msk_maxpy_chunk(const double* win, double* wout, const Vecs* V, int nv, const int* nvdev, const Coefs* A,
                     const double* adev, int negate, int64_t n, int accum, double* partial, const int* stop,
                     hipStream_t s);
+// The first CGS pass fused with stage 1 of the second pass' VecMDot (msplit_k_maxpy_mdot.hip): wout = win - sum_j
+// adev_j V_j (msk_maxpy_chunk's arithmetic, negate = 1) and, from the same registers, the DBR partials of
+// wout . V_v into partial[v * nchunks + c] (v < nv) and of ||wout||^2 into partial[nv * nchunks + c]: bit for bit
+// msk_maxpy_chunk with partials followed by msk_dot_stage1 on wout.  1 <= nv, nv + 1 <= MSK_MAX_GROUP.
+int msk_maxpy_mdot(const double* win, double* wout, const Vecs* V, int nv, const double* adev, int64_t n,
+                   double* partial, int64_t nchunks, const int* stop, hipStream_t s);
 // mode MULT: y = A x; RESID: y = b - A x; SCALED: sc = *sdev, y = A (sc*x) and, when vout != null, vout = sc*x.
 // plane > 0: the operator is a stencil with this many rows per plane (XCD-aware schedule, MSK_TUNE_SPMV_XCD)
 int msk_spmv(int32_t nrows, const int32_t* rowptr, const int32_t* col, const double* val, const double* x,

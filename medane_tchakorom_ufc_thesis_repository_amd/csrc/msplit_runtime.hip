@@ -398,6 +398,66 @@ extern "C" int mspi_maxpy_norm_update(msp_ctx* c, const double* win, double* wou
   return mspi_gm_norm_update(c, g, c->partial, nch, m);
 }
 
+// ---- CGS refinement: pass 1 fused with pass 2's MDot stage 1 (msplit_k_maxpy_mdot.hip), and pass 2's MAXPY.
+// The fused kernel is the default for nv + 1 <= MSPI_MAX_GROUP; MSPLIT_GM_REFINE_FUSED=0 takes the two-kernel
+// sequence everywhere (same bits; the A/B is in DESIGN.md section 5, "CGS refinement").
+extern "C" int mspi_gm_refine_fused(int nv) {
+  static const int on = [] {
+    const char* e = getenv("MSPLIT_GM_REFINE_FUSED");
+    return e ? (atoi(e) ? 1 : 0) : 1;
+  }();
+  return on && nv >= 1 && nv + 1 <= MSPI_MAX_GROUP;
+}
+
+extern "C" const double* mspi_ctx_partial(msp_ctx* c) { return c->partial; }
+
+extern "C" int mspi_maxpy_norm_mdot_basis(msp_ctx* c, const double* win, double* wout, int nv, const double* base,
+                                          int64_t stride, const double* scale, int64_t n, const double* alpha_dev,
+                                          double* c_dev, double* sumsq_dev, const int* stop) {
+  const int64_t nch = nchunks_of(n);
+  if (nch == 0 || nv <= 0) {
+    mspi_set_error(MSP_ERR_ARG_SIZ, "maxpy_norm_mdot on an empty basis");
+    return MSP_ERR_ARG_SIZ;
+  }
+  if (nv + 1 > MSPI_MAX_GROUP || c->reduce == MSP_REDUCE_SEQ) {
+    mspi_set_error(MSP_ERR_SUP, "the fused MAXPY + MDot takes at most %d vectors in the DBR reduction",
+                   MSPI_MAX_GROUP - 1);
+    return MSP_ERR_SUP;
+  }
+  int rc = ensure_partial(c, nch * MSPI_MAX_GROUP);
+  if (rc) return rc;
+  KTimer kt(c, MSP_KERNEL_MAXPY, 8.0 * (double)n * (nv + 2));
+  Vecs vg = {};
+  vg.base = base;
+  vg.stride = stride;
+  vg.scale = scale;
+  KCHK(msk_maxpy_mdot(win, wout, &vg, nv, alpha_dev, n, c->partial, nch, stop, c->stream));
+  if (c_dev) {
+    KCHK(msk_dot_stage2(c->partial, nch, nv, c_dev, stop, c->stream));
+    KCHK(msk_dot_stage2(c->partial + (int64_t)nv * nch, nch, 1, sumsq_dev, stop, c->stream));
+  }
+  return MSP_SUCCESS;
+}
+
+extern "C" int mspi_gm_refine_maxpy2(msp_ctx* c, double* w, int nv, const double* base, int64_t stride,
+                                     const double* scale, int64_t n, const mspi_gmres_refine* rf) {
+  const int64_t nch = nchunks_of(n);
+  if (nch == 0 || nv <= 0) {
+    mspi_set_error(MSP_ERR_ARG_SIZ, "maxpy_norm on an empty basis");
+    return MSP_ERR_ARG_SIZ;
+  }
+  int rc = ensure_partial(c, nch * MSPI_MAX_GROUP);
+  if (rc) return rc;
+  KTimer kt(c, MSP_KERNEL_MAXPY, 8.0 * (double)n * (nv + 2));
+  Vecs vg = {};
+  vg.base = base;
+  vg.stride = stride;
+  vg.scale = scale;
+  Coefs cf = {};
+  KCHK(msk_maxpy_chunk(w, w, &vg, nv, nullptr, &cf, MSPI_REFINE_C(rf), 1, n, 0, c->partial, &rf->skip, c->stream));
+  return MSP_SUCCESS;
+}
+
 extern "C" int mspi_maxpy_accum_basis(msp_ctx* c, double* x, const int* nvdev, const double* base, int64_t stride,
                                       const double* scale, int64_t n, const double* coef_dev, int nv_expected) {
   if (n <= 0) return MSP_SUCCESS;

@@ -818,6 +818,29 @@ class KSP:
         call("msp_ksp_get_pc_type", self.h, C.byref(v))
         return {n: w for w, n in self.PC_TYPES.items()}[v.value]
 
+    # iterative refinement of classical Gram-Schmidt (msp_ksp_set_cgs_refinement): "ifneeded" runs a second pass on
+    # the steps whose first pass cancelled more than it kept, "always" on every step; the decision is taken on the
+    # device.  Double basis, no Jacobi, DBR reduction.
+    CGS_REFINEMENTS = {"never": 0, "ifneeded": 1, "always": 2}
+
+    def set_cgs_refinement(self, refinement: str):                  # KSPGMRESSetCGSRefinementType
+        word = str(refinement).lower()
+        if word not in self.CGS_REFINEMENTS:
+            raise MsplitError(PETSC_ERR_ARG_OUTOFRANGE, f"CGS refinement {refinement!r}: expected one of "
+                                                        f"{sorted(self.CGS_REFINEMENTS)}")
+        call("msp_ksp_set_cgs_refinement", self.h, self.CGS_REFINEMENTS[word])
+
+    def get_cgs_refinement(self) -> str:                            # KSPGMRESGetCGSRefinementType
+        v = C.c_int()
+        call("msp_ksp_get_cgs_refinement", self.h, C.byref(v))
+        return {n: w for w, n in self.CGS_REFINEMENTS.items()}[v.value]
+
+    def get_cgs_refinement_count(self) -> int:
+        """Arnoldi steps of the last solve that ran the second Gram-Schmidt pass."""
+        v = C.c_int32()
+        call("msp_ksp_get_cgs_refinement_count", self.h, C.byref(v))
+        return v.value
+
     @staticmethod
     def _check_jacobi_options(opts: Options, p: str):
         """What -pc_type jacobi is not built with: each is PETSC_ERR_SUP naming the option."""
@@ -855,9 +878,15 @@ class KSP:
             self._check_jacobi_options(opts, p)
         if opts.has("ksp_gmres_modifiedgramschmidt", p):
             raise MsplitError(PETSC_ERR_SUP, "modified Gram-Schmidt is not implemented (CGS only)")
-        rt = opts.get_string("ksp_gmres_cgs_refinement_type", "refine_never", p)
-        if rt.lower() != "refine_never":
-            raise MsplitError(PETSC_ERR_SUP, f"CGS refinement {rt} not implemented (REFINE_NEVER only)")
+        rt = None
+        if opts.has("ksp_gmres_cgs_refinement_type", p):
+            rt = opts.get_string("ksp_gmres_cgs_refinement_type", "refine_never", p).lower()
+            if rt == "refine_always":
+                raise MsplitError(PETSC_ERR_SUP, f"-{p}ksp_gmres_cgs_refinement_type refine_always is not read from "
+                                                 "the options: call set_cgs_refinement(\"always\")")
+            if rt not in ("refine_never", "refine_ifneeded"):
+                raise MsplitError(PETSC_ERR_SUP, f"-{p}ksp_gmres_cgs_refinement_type {rt}: expected refine_never or "
+                                                 "refine_ifneeded")
         nt = opts.get_string("ksp_norm_type", "preconditioned", p).lower()
         if nt not in ("preconditioned", "unpreconditioned"):
             raise MsplitError(PETSC_ERR_SUP, f"-{p}ksp_norm_type {nt} not supported by GMRES")
@@ -888,6 +917,8 @@ class KSP:
             self.set_operator_precision(word)
         if opts.has("pc_type", p):
             self.set_pc_type(pt)
+        if rt is not None:
+            self.set_cgs_refinement(rt[len("refine_"):])
 
     def set_up(self):
         call("msp_ksp_set_up", self.h)

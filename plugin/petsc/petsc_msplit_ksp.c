@@ -15,6 +15,7 @@ typedef struct {
   PetscInt reduction; /* -msplit_reduction dbr|seq on this KSP's prefix; -1: the shared context's order */
   PetscInt basis_precision; /* -msplit_basis_precision double|single|block16: MSP_BASIS_F64 / _F32 / _B16 */
   PetscInt operator_precision; /* -msplit_operator_precision double|single: MSP_OPER_F64 / _F32 */
+  PetscInt cgs_refinement; /* -ksp_gmres_cgs_refinement_type: MSP_CGS_REFINE_NEVER / _IFNEEDED / _ALWAYS */
 } KSP_MSplit;
 
 /* -msplit_reduction: the device reduction order (include/msplit.h msp_ctx_set_reduction).  "seq" is
@@ -245,6 +246,7 @@ static PetscErrorCode KSPSolve_MSplitGMRES_Body(KSP ksp)
   MSPCall(msp_ksp_set_opts(ms->ksp, &o));
   MSPCall(msp_ksp_set_basis_precision(ms->ksp, (int)ms->basis_precision));
   MSPCall(msp_ksp_set_operator_precision(ms->ksp, (int)ms->operator_precision));
+  MSPCall(msp_ksp_set_cgs_refinement(ms->ksp, (int)ms->cgs_refinement));
   PetscCall(VecGetLocalSize(ksp->vec_rhs, &n));
   PetscCall(VecGetArrayRead(ksp->vec_rhs, &b));
   MSPCall(msp_vec_set_values(ms->b, 0, n, b));
@@ -287,6 +289,12 @@ static PetscErrorCode KSPSetFromOptions_MSplitGMRES(KSP ksp, PetscOptionItems *P
   PetscCall(PetscOptionsEnum("-msplit_operator_precision", "storage precision of the operator's values in the Arnoldi products",
                              NULL, MSplitOperatorPrecisions, op, &op, NULL));
   ms->operator_precision = (PetscInt)op;
+  /* PETSc's own option and enum (KSPGMRESCGSRefinementTypes: refine_never, refine_ifneeded, refine_always), whose
+   * values are MSP_CGS_REFINE_*'s: the second Gram-Schmidt pass is decided on the device */
+  PetscEnum rt = (PetscEnum)ms->cgs_refinement;
+  PetscCall(PetscOptionsEnum("-ksp_gmres_cgs_refinement_type", "Type of iterative refinement for classical (unmodified) Gram-Schmidt",
+                             "KSPGMRESSetCGSRefinementType", KSPGMRESCGSRefinementTypes, rt, &rt, NULL));
+  ms->cgs_refinement = (PetscInt)rt;
   PetscCall(PetscOptionsReal("-ksp_gmres_breakdown_tolerance", "restart breakdown tolerance", NULL, ms->breakdowntol,
                              &ms->breakdowntol, NULL));
   PetscOptionsHeadEnd();
