@@ -166,6 +166,12 @@ int msk_box_spmv_mdot(int32_t nx, int64_t P, int64_t n, int d2, const uint8_t* m
 // MAXPY marches where the fused kernel does (planes of whole DBR chunks), else it takes one chunk per workgroup.
 void msk_set_gm_wfree(int on);
 int msk_get_gm_wfree(void);
+// The one-plane form of k_box_maxpy_march (no carried planes, the first vector group's first loads issued under the
+// stencil prologue), where the kernel runs one plane per workgroup.  0: the marched form; 1: the launcher's choice
+// by nv (the default); 2: the one-plane form at every nv; 3: its 8-vector burst.  Default from
+// MSPLIT_MAXPY_PREFETCH; the setter re-keys captured cycles.  Every setting gives the same bits.
+void msk_set_maxpy_prefetch(int mode);
+int msk_get_maxpy_prefetch(void);
 int msk_box_wfree_fits(int32_t nx, int64_t P, int64_t n, int d2);
 int msk_box_maxpy_march(int32_t nx, int64_t P, int64_t n, int d2, const uint8_t* mask, const double* dval, const double* x,
                         const double* sdev, double* wout, const Vecs* V, int nv, const double* adev, double* partial,

@@ -1768,6 +1768,262 @@ __device__ __forceinline__ void march_maxpy_group(double (&u)[2 * kIters], const
   }
 }
 
+// march_maxpy_group in two halves, for the one-plane form of k_box_maxpy_march: the loads of a group's NL streamed
+// vectors VV(g .. g + NL - 1) (the addresses and the issue order of march_maxpy_group: row block by row block),
+// and the arithmetic on what they returned.  The first group's loads are issued under the stencil prologue.
+template <int NL, int VAR>
+__device__ __forceinline__ void maxpy_group_load(double2 (&b)[4][kIters], const Vecs& V, int g, int64_t base) {
+  const double* vp[NL];
+#pragma unroll
+  for (int q = 0; q < NL; ++q) vp[q] = vec_at(V, g + q);
+#pragma unroll
+  for (int j = 0; j < kIters; ++j) {
+#pragma unroll
+    for (int q = 0; q < NL; ++q) {
+      const double2* pv = reinterpret_cast<const double2*>(vp[q] + base + j * (2 * kT));
+      b[q][j] = (VAR & 1) ? ld_nt(pv) : *pv;
+    }
+  }
+}
+
+// one vector, VV(q), into its place in a group that starts at VV(0)
+template <int VAR>
+__device__ __forceinline__ void maxpy_group_load_one(double2 (&b)[4][kIters], const Vecs& V, int q, int64_t base) {
+  const double* vp = vec_at(V, q);
+#pragma unroll
+  for (int j = 0; j < kIters; ++j) {
+    const double2* pv = reinterpret_cast<const double2*>(vp + base + j * (2 * kT));
+    b[q][j] = (VAR & 1) ? ld_nt(pv) : *pv;
+  }
+}
+
+// SELF: the group's last vector is x, whose 16 values of this lane are read back from the LDS window (xs: the
+// lane's first pair in it), the doubles the kernel stored there itself.
+template <int G, bool SELF>
+__device__ __forceinline__ void maxpy_group_apply(double (&u)[2 * kIters], const double2 (&b)[4][kIters],
+                                                  const Vecs& V, const double* __restrict__ adev, int g,
+                                                  const double* xs) {
+  double a[G], sv[G];
+#pragma unroll
+  for (int q = 0; q < G; ++q) {
+    a[q] = -adev[g + q];
+    sv[q] = vec_scale(V, g + q);
+  }
+#pragma unroll
+  for (int j = 0; j < kIters; ++j) {
+    double p0[G], p1[G];
+#pragma unroll
+    for (int q = 0; q < G; ++q) {
+      const double2 v = (SELF && q == G - 1) ? *reinterpret_cast<const double2*>(xs + j * (2 * kT)) : b[q][j];
+      p0[q] = v.x * sv[q];
+      p1[q] = v.y * sv[q];
+    }
+    const double s0 = group_sum<G>(a, p0), s1 = group_sum<G>(a, p1);
+    if constexpr (G == 1) {
+      u[2 * j] = s0 + u[2 * j];
+      u[2 * j + 1] = s1 + u[2 * j + 1];
+    } else {
+      u[2 * j] = u[2 * j] + s0;
+      u[2 * j + 1] = u[2 * j + 1] + s1;
+    }
+  }
+}
+
+// The front of box_maxpy_plane: the prologue's loads with the NPF first basis vectors' loads behind them, the
+// window, and W = A (sc x) for the lane's 16 rows in u.  NPF is a template parameter so that all of it is one
+// straight run of code (a run-time count puts the vector loads in branches of their own, and the compiler then
+// moves the x(z) loads below them).
+#define MSK_LOAD_FENCE(p_)                        \
+  asm volatile("" : : "v"(p_) : "memory");        \
+  __builtin_amdgcn_sched_barrier(0)
+template <int VAR, int NPF>
+__device__ __forceinline__ void box_plane_front(int32_t nx, int64_t P, int32_t nz, int32_t z, int64_t c0,
+                                                const uint8_t* __restrict__ mask, const double* __restrict__ dval,
+                                                const double* __restrict__ x, const double* __restrict__ sdev,
+                                                const Vecs& V, double* sx, double (&u)[2 * kIters],
+                                                double2 (&ba)[4][kIters]) {
+  const int t = threadIdx.x;
+  const int64_t base = c0 + 2 * t;
+  const int nh = nx / 2;
+  const double sc = *sdev;
+  double v[7];
+  march_values<false>(dval, v);
+  // The loads in the order their values are needed: what the window takes first, then x(z -+ 1) and the mask,
+  // then the vector group.  Left alone the compiler issues x(z) last, right before its use, and the window's wait
+  // drains everything.  The fences keep each stage where it is written (to the compiler they may write through
+  // the pointer they are given, so no load moves across them; they emit nothing), and they can only do that
+  // inside one basic block, so no load here is conditional: a lane without a halo pair, and every lane of a plane
+  // without a neighbour, reads its own first pair of x(z) once more (an address it reads anyway) and takes 0.0.
+  const double* own = x + base;
+  dx2 xc[kIters], xm[kIters], xp[kIters];
+#pragma unroll
+  for (int j = 0; j < kIters; ++j) xc[j] = *reinterpret_cast<const dx2*>(own + j * (2 * kT));
+  const bool hasl = t < nh && c0 - nx >= 0, hash = t < nh && c0 + kChunk + nx <= (int64_t)nz * P;
+  dx2 hl = *reinterpret_cast<const dx2*>(hasl ? x + c0 - nx + 2 * t : own);
+  dx2 hh = *reinterpret_cast<const dx2*>(hash ? x + c0 + kChunk + 2 * t : own);
+  MSK_LOAD_FENCE(own);
+  const bool hasm = z > 0, hasp = z + 1 < nz;
+  uint32_t m[kIters];
+#pragma unroll
+  for (int j = 0; j < kIters; ++j) xm[j] = *reinterpret_cast<const dx2*>(hasm ? own - P + j * (2 * kT) : own);
+#pragma unroll
+  for (int j = 0; j < kIters; ++j) xp[j] = *reinterpret_cast<const dx2*>(hasp ? own + P + j * (2 * kT) : own);
+#pragma unroll
+  for (int j = 0; j < kIters; ++j) m[j] = *reinterpret_cast<const uint16_t*>(mask + base + j * (2 * kT));
+  MSK_LOAD_FENCE(own);
+  if constexpr (NPF > 0) maxpy_group_load<NPF, VAR>(ba, V, 0, base);
+  MSK_LOAD_FENCE(own);
+  if (!hasl) hl = dx2{0.0, 0.0};
+  if (!hash) hh = dx2{0.0, 0.0};
+#pragma unroll
+  for (int j = 0; j < kIters; ++j) {
+    if (!hasm) xm[j] = dx2{0.0, 0.0};
+    if (!hasp) xp[j] = dx2{0.0, 0.0};
+  }
+#pragma unroll
+  for (int j = 0; j < kIters; ++j) *reinterpret_cast<dx2*>(sx + nx + j * (2 * kT) + 2 * t) = xc[j];
+  if (t < nh) {
+    *reinterpret_cast<dx2*>(sx + 2 * t) = hl;
+    *reinterpret_cast<dx2*>(sx + nx + kChunk + 2 * t) = hh;
+  }
+  for (int i = t + kT; i < nh; i += kT) {
+    *reinterpret_cast<double2*>(sx + 2 * i) =
+        c0 - nx >= 0 ? *reinterpret_cast<const double2*>(x + c0 - nx + 2 * i) : make_double2(0.0, 0.0);
+    *reinterpret_cast<double2*>(sx + nx + kChunk + 2 * i) =
+        c0 + kChunk + nx <= (int64_t)nz * P ? *reinterpret_cast<const double2*>(x + c0 + kChunk + 2 * i)
+                                            : make_double2(0.0, 0.0);
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < kIters; ++j) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const int e = j * (2 * kT) + 2 * t + q + nx;
+      const uint32_t mr = (m[j] >> (8 * q)) & 255u;
+      const double xq[7] = {q ? xm[j].y : xm[j].x, sx[e - nx], sx[e - 1], sx[e], sx[e + 1], sx[e + nx],
+                            q ? xp[j].y : xp[j].x};
+      double s = 0.0;
+#pragma unroll
+      for (int k = 0; k < 7; ++k)
+        if (mr & (1u << k)) s = s + v[k] * (xq[k] * sc);
+      u[2 * j + q] = s;
+    }
+  }
+}
+
+#undef MSK_LOAD_FENCE
+// k_box_maxpy_march for one plane per workgroup (zt = 1), the default.  The same rows, the same loads and the same
+// arithmetic as the marched form's single plane, in another order of issue:
+//  * no carried planes: x(z -+ 1) live only until W is formed, and x(z) -- W's centre term and the SELF vector --
+//    is read back from the window the kernel wrote (the same doubles);
+//  * the loads of the first vector group's first two vectors are issued right behind the prologue's own loads,
+//    before the barrier.  Vector-memory loads return in issue order, so the window's wait leaves them in flight
+//    (a partial vmcnt: at most 8 + 8 + 8 + 16 = 40 loads behind x(z) and the halo, within the counter's 63) and
+//    the barrier, the LDS round trip and W's arithmetic run under them.
+//    A box with nx > 2 kT fills the rest of its halo lines after the barrier and so waits for everything there;
+//  * WIDE: two groups of four per burst (64 loads per lane, k_maxpy_chunk's shape).
+// Both widths run one wave per SIMD (362 and 436 registers per lane of the unified file; the narrow one does not
+// compile into 256 without scratch), so the launcher takes this form only from the nv where its better rate per
+// vector has paid for the prologue no second workgroup covers (msk_box_maxpy_march).
+template <int VAR, bool NTY, bool WIDE>
+__device__ __forceinline__ void box_maxpy_plane(int32_t nx, int64_t P, int32_t nz, int xcd,
+                                                const uint8_t* __restrict__ mask, const double* __restrict__ dval,
+                                                const double* __restrict__ x, const double* __restrict__ sdev,
+                                                double* __restrict__ wout, const Vecs& V, int nv,
+                                                const double* __restrict__ adev, double* __restrict__ partial,
+                                                double* sx, double* red) {
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const int64_t cpp = P / kChunk;
+  int64_t tile, zg;
+  if (xcd & 1) {
+    const int64_t per = cpp / 8, slot = blockIdx.x / 8;
+    tile = (blockIdx.x % 8) * per + slot % per;
+    zg = slot / per;
+  } else {
+    tile = blockIdx.x % cpp;
+    zg = blockIdx.x / cpp;
+  }
+  if (xcd & 2) zg = nz - 1 - zg;
+  const int32_t z = (int32_t)zg;
+  const int64_t c = (int64_t)z * cpp + tile, c0 = c * kChunk, base = c0 + 2 * t;
+  const int jrem = nv & 3;
+  // the first group streams nfirst vectors, VV(0 .. nfirst - 1); the first two of them are loaded under the
+  // prologue (with x(z), x(z -+ 1) and the mask still in registers no more fit beside them at two waves per
+  // SIMD), the others once W is formed
+  double2 ba[4][kIters];
+  double u[2 * kIters];
+  const int nfirst = nv <= 3 ? nv - 1 : jrem ? jrem : nv == 4 ? 3 : 4;
+  if (nfirst >= 2) box_plane_front<VAR, 2>(nx, P, nz, z, c0, mask, dval, x, sdev, V, sx, u, ba);
+  else if (nfirst == 1) box_plane_front<VAR, 1>(nx, P, nz, z, c0, mask, dval, x, sdev, V, sx, u, ba);
+  else box_plane_front<VAR, 0>(nx, P, nz, z, c0, mask, dval, x, sdev, V, sx, u, ba);
+  if (nfirst >= 3) maxpy_group_load_one<VAR>(ba, V, 2, base);
+  if (nfirst == 4) maxpy_group_load_one<VAR>(ba, V, 3, base);
+  // u -= sum_j h_j VV(j): leading nv & 3 vectors, then groups of four; VV(nv - 1) = x from the window
+  const double* xs = sx + nx + 2 * t;
+  if (nv <= 3) {
+    if (jrem == 3) maxpy_group_apply<3, true>(u, ba, V, adev, 0, xs);
+    else if (jrem == 2) maxpy_group_apply<2, true>(u, ba, V, adev, 0, xs);
+    else maxpy_group_apply<1, true>(u, ba, V, adev, 0, xs);
+  } else {
+    int g = jrem;
+    bool tail = false;  // the last group (three vectors and x) is already in ba
+    if (jrem == 3) maxpy_group_apply<3, false>(u, ba, V, adev, 0, xs);
+    else if (jrem == 2) maxpy_group_apply<2, false>(u, ba, V, adev, 0, xs);
+    else if (jrem == 1) maxpy_group_apply<1, false>(u, ba, V, adev, 0, xs);
+    else if (nv == 4) tail = true;
+    else {
+      maxpy_group_apply<4, false>(u, ba, V, adev, 0, xs);
+      g = 4;
+    }
+    if constexpr (WIDE) {
+      double2 bb[4][kIters];
+#pragma unroll 1
+      for (; g + 8 < nv; g += 8) {
+        maxpy_group_load<4, VAR>(ba, V, g, base);
+        maxpy_group_load<4, VAR>(bb, V, g + 4, base);
+        maxpy_group_apply<4, false>(u, ba, V, adev, g, xs);
+        maxpy_group_apply<4, false>(u, bb, V, adev, g + 4, xs);
+      }
+      if (g + 4 < nv) {  // one group of four left, and the last group behind it
+        maxpy_group_load<4, VAR>(ba, V, g, base);
+        maxpy_group_load<3, VAR>(bb, V, nv - 4, base);
+        maxpy_group_apply<4, false>(u, ba, V, adev, g, xs);
+        maxpy_group_apply<4, true>(u, bb, V, adev, nv - 4, xs);
+      } else {
+        if (!tail) maxpy_group_load<3, VAR>(ba, V, nv - 4, base);
+        maxpy_group_apply<4, true>(u, ba, V, adev, nv - 4, xs);
+      }
+    } else {
+#pragma unroll 1
+      for (; g + 4 < nv; g += 4) {
+        maxpy_group_load<4, VAR>(ba, V, g, base);
+        maxpy_group_apply<4, false>(u, ba, V, adev, g, xs);
+      }
+      if (!tail) maxpy_group_load<3, VAR>(ba, V, nv - 4, base);
+      maxpy_group_apply<4, true>(u, ba, V, adev, nv - 4, xs);
+    }
+  }
+  double acc = 0.0;
+#pragma unroll
+  for (int j = 0; j < kIters; ++j) {
+    const double r0 = u[2 * j], r1 = u[2 * j + 1];
+    if constexpr (NTY) {
+      dx2 o;
+      o.x = r0;
+      o.y = r1;
+      __builtin_nontemporal_store(o, reinterpret_cast<dx2*>(wout + base + j * (2 * kT)));
+    } else {
+      *reinterpret_cast<double2*>(wout + base + j * (2 * kT)) = make_double2(r0, r1);
+    }
+    acc = acc + r0 * r0;
+    acc = acc + r1 * r1;
+  }
+  acc = wave_butterfly(acc);
+  if (lane == 0) red[wv] = acc;
+  __syncthreads();
+  if (t == 0) partial[c] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
 // The GMRES step's CGS VecMAXPY for a box stencil whose fused MatMult+MDot (k_box_spmv_mdot_march, y = null)
 // did not store W: this kernel recomputes W = A (sc x) for its rows on the same chunk tiles, with the same
 // terms in the same order (bitwise that kernel's W), then wout = W - sum_j h_j VV(j) in k_maxpy_chunk's
@@ -1776,7 +2032,8 @@ __device__ __forceinline__ void march_maxpy_group(double (&u)[2 * kIters], const
 // k_maxpy_chunk<false, true, .> does.  Bytes per row: the presence byte, x once (+ the tile's halo lines),
 // nv - 1 basis vectors and wout, against 8 (nv + 2) for k_maxpy_chunk plus the 8 the MatMult spent storing W.
 // xcd & 1: XCD-contiguous eighths of each plane's tiles; xcd & 2: top plane groups first.
-template <int VAR, bool NTY>
+// PF: 0 the marched form (any zt); 1, 2: the one-plane form (box_maxpy_plane; zt = 1 only), 2 its wide burst.
+template <int VAR, bool NTY, int PF>
 __global__ __launch_bounds__(kT) void k_box_maxpy_march(int32_t nx, int64_t P, int32_t nz, int32_t zt, int xcd,
                                                         const uint8_t* __restrict__ mask,
                                                         const double* __restrict__ dval,
@@ -1788,6 +2045,10 @@ __global__ __launch_bounds__(kT) void k_box_maxpy_march(int32_t nx, int64_t P, i
   extern __shared__ __attribute__((aligned(16))) char smem[];
   double* sx = reinterpret_cast<double*>(smem);  // window of plane z: kChunk + 2 nx doubles
   __shared__ double red[4];
+  if constexpr (PF != 0) {
+    box_maxpy_plane<VAR, NTY, PF == 2>(nx, P, nz, xcd, mask, dval, x, sdev, wout, V, nv, adev, partial, sx, red);
+    return;
+  }
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
   const int64_t cpp = P / kChunk;
   int64_t tile, zg;
@@ -2280,6 +2541,22 @@ extern "C" void msk_set_gm_wfree(int on) {
   ++msk_shape_epoch;
 }
 extern "C" int msk_get_gm_wfree(void) { return msk_gm_wfree; }
+// The one-plane form of k_box_maxpy_march (box_maxpy_plane: no carried planes, the first vector group's first loads
+// under the stencil prologue), taken where the kernel runs one plane per workgroup.  0: the marched form; 1: the
+// launcher's choice by nv (msk_box_maxpy_march); 2: the one-plane form at every nv; 3: its 8-vector burst (A/B).
+// MSPLIT_MAXPY_PREFETCH sets the default; msk_set_maxpy_prefetch switches it (A/B, tests) and re-keys captured
+// cycles.  Every setting gives the same bits.
+constexpr int kMaxpyPrefetchDefault = 1;
+__attribute__((visibility("hidden"))) int msk_maxpy_prefetch = [] {
+  const char* e = getenv("MSPLIT_MAXPY_PREFETCH");
+  const int v = e ? atoi(e) : kMaxpyPrefetchDefault;
+  return v < 0 || v > 3 ? kMaxpyPrefetchDefault : v;
+}();
+extern "C" void msk_set_maxpy_prefetch(int mode) {
+  msk_maxpy_prefetch = mode < 0 || mode > 3 ? 0 : mode;
+  ++msk_shape_epoch;
+}
+extern "C" int msk_get_maxpy_prefetch(void) { return msk_maxpy_prefetch; }
 
 static inline XcdMap xcd_map(int32_t nrows, int64_t plane) {
   XcdMap m = {0, 0, 0};
@@ -2873,12 +3150,29 @@ extern "C" int msk_box_maxpy_march(int32_t nx, int64_t P, int64_t n, int d2, con
     const char* e = getenv("MSPLIT_MAXPY_MARCH_U2");
     return e ? atoi(e) : 0;
   }();
-#define MSK_BMM(VAR_, NT_)                                                                                      \
-  k_box_maxpy_march<VAR_, NT_><<<dim3((unsigned)grid), dim3(kT), lds, s>>>(nx, P, nz, zt, xcd, mask, dval, x,  \
-                                                                           sdev, wout, *V, nv, adev, partial, stop)
-  if (u2 && vec_var() && nty) MSK_BMM(33, true);
-  else if (vec_var()) { if (nty) MSK_BMM(1, true); else MSK_BMM(1, false); }
-  else { if (nty) MSK_BMM(0, true); else MSK_BMM(0, false); }
+#define MSK_BMM(VAR_, NT_, PF_)                                                                              \
+  k_box_maxpy_march<VAR_, NT_, PF_><<<dim3((unsigned)grid), dim3(kT), lds, s>>>(                                \
+      nx, P, nz, zt, xcd, mask, dval, x, sdev, wout, *V, nv, adev, partial, stop)
+#define MSK_BMM2(PF_)                                                              \
+  do {                                                                             \
+    if (vec_var()) { if (nty) MSK_BMM(1, true, PF_); else MSK_BMM(1, false, PF_); } \
+    else { if (nty) MSK_BMM(0, true, PF_); else MSK_BMM(0, false, PF_); }           \
+  } while (0)
+  // the one-plane form where one plane per workgroup runs (MSPLIT_MAXPY_ZT > 1 keeps the marched form)
+  // By nv (mode 1): the one-plane form runs one wave per SIMD (its registers do not fit two), so nothing covers a
+  // workgroup's prologue but its own prefetch, and a launch costs about 28 us more at nv = 1 (256^3: 93 against
+  // 64 us); each further vector costs it 20.2 us against the marched form's 22.4, so it is level at nv = 12..14 and
+  // ahead beyond the run-to-run spread from nv = 16 on, at 256^3 and at 512 x 512 x 256 alike (nv = 16: 357 against
+  // 370 us and 1475 against 1556; nv = 30: 649 against 683 and 2705 against 2833).  The 8-vector burst is never
+  // ahead of the 4-vector one.  profiles/maxpy_prefetch/new_by_nv.jsonl (tools/maxpy_march_ab.py).
+  constexpr int kOnePlaneFromNv = 16;
+  const int mode = zt == 1 ? msk_maxpy_prefetch : 0;
+  const int pf = mode == 1 ? (nv >= kOnePlaneFromNv ? 2 : 0) : mode;
+  if (pf == 3) MSK_BMM2(2);
+  else if (pf == 2) MSK_BMM2(1);
+  else if (u2 && vec_var() && nty) MSK_BMM(33, true, 0);
+  else MSK_BMM2(0);
+#undef MSK_BMM2
 #undef MSK_BMM
   return (int)hipGetLastError();
 }
