@@ -36,19 +36,19 @@
  *            written by the MatMult (fused with MDot where the operator allows) and read by the MAXPY, which writes
  *            a different vector than it reads (an in-place MAXPY measured 5 % slower, same box).
  *   f32      MSP_BASIS_F32 (msp_ksp_set_basis_precision): the basis is stored as float and the step is always
- *            MatMult, MDot, MAXPY as three kernels (msplit_cb.hip) over two f64 n-vectors: W and the "current
+ *            MatMult, MDot, MAXPY as three kernels (msplit_cgs_basis.hip) over two f64 n-vectors: W and the "current
  *            vector", the newest basis vector's rounded values as doubles, which is the MatMult's input -- so every
  *            operator's scaled MatMult serves unchanged.  VV(it+1) = rnd(W - sum ...) is rounded when stored and
  *            its norm is the rounded values' norm; everything else is the same f64 arithmetic.  Neither opfuse nor
  *            wfree is taken, and the MDot / MAXPY variant flags of MSPLIT_TUNING do not apply.
- *   block16  MSP_BASIS_B16: the f32 step with another stored format (msplit_cb16.hip): 16-bit integers with one
+ *   block16  MSP_BASIS_B16: the f32 step with another stored format (the same kernels' B16): 16-bit integers with one
  *            power-of-two exponent per DBR chunk and vector, the rounding rule of include/msplit.h.  Same launches,
  *            same two f64 n-vectors, same arithmetic; the whole double exponent range is representable and a
  *            non-finite entry ends the solve.  Inside one restart cycle the recurrence residual can run ahead of
  *            the true one by about 2^-13 of the cycle's initial residual (the next restart recomputes it in f64):
  *            for inexact inner solves and fixed-iteration steps, not for gaining many digits in a single cycle.
  *   jacobi   MSP_PC_JACOBI (msp_ksp_set_pc_type): PETSc's left Jacobi with the preconditioned norm on the f64 basis.
- *            MatMult, MDot, MAXPY as three kernels (msplit_pcj.hip); the MatMult stores the raw W and the two CGS
+ *            MatMult, MDot, MAXPY as three kernels (msplit_cgs_basis.hip); the MatMult stores the raw W and the two CGS
  *            kernels form dinv .* W in registers as they load it (8 more bytes per row each, no rewrite of W).  The
  *            cycle's first kernel multiplies the initial residual by dinv in place; ||dinv .* b|| serves the
  *            convergence test's rnorm0.  Neither opfuse nor wfree is taken; the recurrence is unchanged.

@@ -2,8 +2,8 @@
 // (MSP_OPER_F32, msp_ksp_set_operator_precision), for gfx950.
 //
 // The copy holds one 8-byte word per stored entry, in CSR order: {int32 col, float val}, val = (float)a -- round to
-// nearest even, gradual underflow, the conversion of msplit_cb.hip.  The f64 kernel k_spmv_lds8 streams 12 bytes
-// per entry (two arrays, two staging loops); this one streams 8 bytes in one loop.  All arithmetic stays f64:
+// nearest even, gradual underflow, msplit_cgs_basis.hip's F32 conversion.  The f64 kernel k_spmv_lds8 streams 12
+// bytes per entry (two arrays, two staging loops); this one streams 8 bytes in one loop.  All arithmetic stays f64:
 //   s = s + (double)val_k * (x[col_k] * sc), entries in CSR order from 0.0, never contracted,
 // which is k_spmv_lds8's SCALED sum statement for statement, so the product equals, bit for bit, the f64 kernel's
 // product on a matrix whose values are (double)(float)a.  The row-block schedule (XcdMap) is the f64 kernel's: it

@@ -217,7 +217,7 @@ int mspi_gm_refine_update(msp_ctx *ctx, mspi_gmres_dev g, mspi_gmres_refine *rf,
                           int64_t nchunks, int m);
 /* the context's DBR partial buffer (valid after mspi_reserve_partial; enqueued work points at it) */
 const double *mspi_ctx_partial(msp_ctx *ctx);
-/* ---- MSP_BASIS_F32: the same steps over a basis stored as float (msplit_cb.hip), VV(j) = base + j*stride with its
+/* ---- MSP_BASIS_F32: the same steps over a basis stored as float (msplit_cgs_basis.hip), VV(j) = base + j*stride with its
    value (double)VV(j)[i] * scale[j]; all arithmetic f64, DBR only.  rnd(v) = (double)(float)v. ---- */
 /* cur = rnd(r) (f64; may be r itself), v0 = the same as float, sumsq_dev[0] = sum rnd(r)^2 */
 int mspi_cb_round_store(msp_ctx *ctx, const double *r, double *cur, float *v0, int64_t n, double *sumsq_dev,
@@ -231,7 +231,7 @@ int mspi_cb_maxpy_norm_update(msp_ctx *ctx, const double *win, double *cur, floa
 int mspi_cb_accum(msp_ctx *ctx, double *x, const int *nvdev, const float *base, int64_t stride, const double *scale,
                   int64_t n, const double *coef_dev, int nv_expected);
 /* ---- MSP_BASIS_B16: the same steps over a basis stored as int16 with one int32 exponent per DBR chunk and vector
-   (msplit_cb16.hip), VV(j) = base + j*stride, its exponents ebase + j*ceil(n/4096); all arithmetic f64, DBR only.
+   (msplit_cgs_basis.hip), VV(j) = base + j*stride, its exponents ebase + j*ceil(n/4096); all arithmetic f64, DBR only.
    rnd16 is the rule of include/msplit.h. ---- */
 /* cur = rnd16(r) (f64; may be r itself), v0 / e0 = the same as block16, sumsq_dev[0] = sum rnd16(r)^2 */
 int mspi_cb16_round_store(msp_ctx *ctx, const double *r, double *cur, int16_t *v0, int32_t *e0, int64_t n,
@@ -244,7 +244,7 @@ int mspi_cb16_maxpy_norm_update(msp_ctx *ctx, const double *win, double *cur, in
                                 int64_t n, mspi_gmres_dev g, int m, const int *stop);
 int mspi_cb16_accum(msp_ctx *ctx, double *x, const int *nvdev, const int16_t *base, int64_t stride,
                     const int32_t *ebase, const double *scale, int64_t n, const double *coef_dev, int nv_expected);
-/* ---- MSP_PC_JACOBI: left Jacobi preconditioning fused into the CGS kernels over the f64 basis (msplit_pcj.hip);
+/* ---- MSP_PC_JACOBI: left Jacobi preconditioning fused into the CGS kernels over the f64 basis (msplit_cgs_basis.hip);
    dinv = n doubles from mspi_pcj_diag_inv, w = W .* dinv formed as W is loaded (W stays as the MatMult wrote it),
    everything after that multiply the f64 step's arithmetic; DBR only. ---- */
 /* d_i = a_ii (0.0 where row i stores none); MSP_ERR_SUP unless A holds its CSR arrays (not row-compressed, not

@@ -208,7 +208,7 @@ int msk_stencil_spmv(int dim, int32_t nx, int32_t ny, int32_t nz, int64_t nrows,
 int msk_box_stencil(int dim, int32_t nx, int32_t ny, int32_t nz, int64_t nrows, int lo, int hi, const BoxCoef* cf,
                     int32_t* rowptr, int32_t* col, double* val, hipStream_t s);
 int msk_blas1(int op, double* y, const double* x, const double* z, double alpha, int64_t n, hipStream_t s);
-// ---- compressed-basis GMRES (msplit_cb.hip): the Krylov basis in HBM as float, VV(j) = vb + j*stride (stride a
+// ---- compressed-basis GMRES (msplit_cgs_basis.hip, F32): the Krylov basis in HBM as float, VV(j) = vb + j*stride (stride a
 // multiple of 1024), its value (double)VV(j)[i] * scale[j]; all arithmetic f64, DBR lane map and order.
 #define MSK_CB_MAX_GROUP 32
 // cur = rnd(r) as f64 (may be r itself), v0 = the same as f32, partial[c] = DBR partials of sum rnd(r)^2
@@ -224,7 +224,7 @@ int msk_cb_maxpy_norm(const double* win, double* cur, float* vout, const float* 
 // x = x + (0 + sum_j coef_j VV(j)), j < *nvdev
 int msk_cb_accum(double* x, const int* nvdev, const float* vb, int64_t stride, const double* scale,
                  const double* coef, int64_t n, const int* stop, hipStream_t s);
-// ---- block-scaled basis (msplit_cb16.hip): the Krylov basis in HBM as int16 with one int32 power-of-two exponent
+// ---- block-scaled basis (msplit_cgs_basis.hip, B16): the Krylov basis in HBM as int16 with one int32 power-of-two exponent
 // per DBR chunk and vector, VV(j) = vb + j*stride (stride a multiple of 2048), its exponents eb + j*nchunks
 // (nchunks = ceil(n / 4096)); element i of chunk c reads ldexp(q_i, eb[j*nchunks + c] - 15) * scale[j], NaN where
 // the exponent is INT32_MIN (the chunk held a NaN or an inf).  Same arithmetic and order as the msk_cb_* kernels.
@@ -241,8 +241,9 @@ int msk_cb16_maxpy_norm(const double* win, double* cur, int16_t* vout, int32_t* 
 // x = x + (0 + sum_j coef_j VV(j)), j < *nvdev
 int msk_cb16_accum(double* x, const int* nvdev, const int16_t* vb, int64_t stride, const int32_t* eb,
                    const double* scale, const double* coef, int64_t n, const int* stop, hipStream_t s);
-// ---- left Jacobi preconditioning of GMRES (msplit_pcj.hip): the f64 basis, VV(j) = vb + j*stride, its value
-// VV(j)[i] * scale[j]; w = W .* dinv formed in registers; DBR lane map and order, the f64 step's arithmetic.
+// ---- left Jacobi preconditioning of GMRES (msplit_cgs_basis.hip, F64 with WDinv): the f64 basis, VV(j) = vb +
+// j*stride, its value VV(j)[i] * scale[j]; w = W .* dinv formed in registers; DBR lane map and order, the f64 step's
+// arithmetic.
 // out_i = a_ii of the CSR (0.0 where row i stores none); invert: 1 / a_ii, and 1.0 where a_ii is +-0.0 or absent
 int msk_pcj_diag(const int32_t* rowptr, const int32_t* col, const double* val, int32_t n, double* out, int invert,
                  hipStream_t s);

@@ -472,7 +472,7 @@ extern "C" int mspi_maxpy_accum_basis(msp_ctx* c, double* x, const int* nvdev, c
   return MSP_SUCCESS;
 }
 
-// ---- MSP_BASIS_F32 (msplit_cb.hip): the same four steps over a float basis.  Byte counts: 4 per basis element,
+// ---- MSP_BASIS_F32 (msplit_cgs_basis.hip): the same four steps over a float basis.  Byte counts: 4 per basis element,
 // 8 per element of the f64 vectors (W, the current vector, x).  The MSPLIT_TUNING variants of the f64 MDot / MAXPY
 // do not apply: each step has one kernel.
 extern "C" int mspi_cb_round_store(msp_ctx* c, const double* r, double* cur, float* v0, int64_t n, double* sumsq_dev,
@@ -536,7 +536,7 @@ extern "C" int mspi_cb_accum(msp_ctx* c, double* x, const int* nvdev, const floa
   return MSP_SUCCESS;
 }
 
-// ---- MSP_BASIS_B16 (msplit_cb16.hip): the same four steps over an int16 basis with one int32 exponent per DBR
+// ---- MSP_BASIS_B16 (msplit_cgs_basis.hip): the same four steps over an int16 basis with one int32 exponent per DBR
 // chunk and vector.  Byte counts: 2 per basis element plus 4 per chunk and vector, 8 per element of the f64 vectors.
 extern "C" int mspi_cb16_round_store(msp_ctx* c, const double* r, double* cur, int16_t* v0, int32_t* e0, int64_t n,
                                      double* sumsq_dev, const int* stop) {
@@ -604,7 +604,7 @@ extern "C" int mspi_cb16_accum(msp_ctx* c, double* x, const int* nvdev, const in
   return MSP_SUCCESS;
 }
 
-// ---- MSP_PC_JACOBI (msplit_pcj.hip): the stored-W step over the f64 basis with w = W .* dinv formed in the CGS
+// ---- MSP_PC_JACOBI (msplit_cgs_basis.hip): the stored-W step over the f64 basis with w = W .* dinv formed in the CGS
 // kernels.  Byte counts: the f64 kernels' plus 8 per row for dinv.  The MSPLIT_TUNING variants of the f64 MDot /
 // MAXPY do not apply: each step has one kernel.
 extern "C" int mspi_pcj_apply_norm(msp_ctx* c, const double* r, const double* dinv, double* z, int64_t n,

@@ -2,7 +2,7 @@
 
 TEST INFRASTRUCTURE ONLY.  block16(v) is the rule of include/msplit.h in numpy -- frexp, ldexp, rint, clip, ldexp
 per DBR chunk of 4096 elements -- and gmres is tests/basis_twin.py's solve with that rounding at the two places
-where a basis vector is stored.  The device (msplit_cb16.hip) is held to both bit for bit.
+where a basis vector is stored.  The device (msplit_cgs_basis.hip) is held to both bit for bit.
 """
 from __future__ import annotations
 

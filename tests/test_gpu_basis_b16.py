@@ -1,7 +1,7 @@
 """Block-scaled basis GMRES (-msplit_basis_precision block16, MSP_BASIS_B16) on the GPU.
 
 The Krylov basis is stored in HBM as 16-bit integers with one power-of-two exponent per DBR chunk and vector
-(msplit_cb16.hip) and every other number stays double, so the device solve is held to the Python twin with the
+(msplit_cgs_basis.hip) and every other number stays double, so the device solve is held to the Python twin with the
 block16 rounding (tests/basis_b16.py) bit for bit: iteration count, reason, residual norm, every history entry and
 x.  The shapes are those of tests/test_gpu_basis_f32.py, the smallest that reach each path of the four kernels: a
 partial chunk only, odd n, one full chunk plus a tail, two full chunks plus a tail, more than 32 vectors, GMRES(1),

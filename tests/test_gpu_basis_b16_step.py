@@ -1,4 +1,4 @@
-"""The four block16 launchers (mspi_cb16_*, msplit_cb16.hip) one call at a time, on guarded buffers.
+"""The four block16 launchers (mspi_cb16_*, msplit_cgs_basis.hip) one call at a time, on guarded buffers.
 
 The f64 operands -- W, the current vector, x, the recurrence block -- are a tests/gmres_step.py StepWork; the block16
 basis is a buffer of this module laid out as msp_ksp_set_up lays it out: 33 vectors of stride = n rounded up to 2048

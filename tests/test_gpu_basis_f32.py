@@ -2,7 +2,7 @@
 
 The Krylov basis is stored in HBM as float and every other number stays double, so the device solve is held to the
 Python twin with the f32 rounding (tests/basis_twin.py) bit for bit: iteration count, reason, residual norm, every
-history entry and x.  The shapes are the smallest that reach each path of the four kernels (msplit_cb.hip): a
+history entry and x.  The shapes are the smallest that reach each path of the four kernels (msplit_cgs_basis.hip): a
 partial chunk only, odd n, one full chunk plus a tail, two full chunks plus a tail, more than 32 vectors, GMRES(1),
 many restarts; every SpMV route feeds the same step; f32 subnormals and overflow behave as numpy's conversion.
 """

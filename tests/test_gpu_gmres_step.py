@@ -133,6 +133,7 @@ KINDS.update({
                                fused=lambda nv: nv <= 32),
     "f32-64x64x3": Kind("f32", _box(64, 64, 3), reached=_storage("dv")),
     "f32-37x11x9": Kind("f32", _box(37, 11, 9), reached=_storage("dv")),
+    "f32-100x30x9": Kind("f32", _box(100, 30, 9), reached=_storage("dv")),     # full chunks, then a ragged last one
 })
 
 _built = {}

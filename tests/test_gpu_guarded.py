@@ -441,8 +441,8 @@ F32_CASES = {
 
 @pytest.mark.parametrize("case", list(F32_CASES))
 def test_gmres_f32_basis_guarded(ctx, oracle, case):
-    """-msplit_basis_precision single (msplit_cb.hip) with b and x guarded, against the f32 twin: n an exact chunk
-    multiple (the full-chunk path alone), a full chunk plus a tail, and more than 32 basis vectors over full
+    """-msplit_basis_precision single (msplit_cgs_basis.hip) with b and x guarded, against the f32 twin: n an exact
+    chunk multiple (the full-chunk path alone), a full chunk plus a tail, and more than 32 basis vectors over full
     chunks (MDot and BuildSoln in two groups)."""
     (nx, ny, nz), o = F32_CASES[case]
     O = oracle.poisson3d_rows(nx, ny, nz, 0, nz)

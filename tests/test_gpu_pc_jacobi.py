@@ -1,7 +1,7 @@
 """Left Jacobi preconditioning of GMRES (-pc_type jacobi, MSP_PC_JACOBI) on the GPU.
 
 PETSc's PCJACOBI (diagonal) on the left with the preconditioned norm, fused into the CGS kernels
-(msplit_pcj.hip).  Every solve is held to the Python twin (tests/pc_twin.py, itself pinned to the C oracle by
+(msplit_cgs_basis.hip).  Every solve is held to the Python twin (tests/pc_twin.py, itself pinned to the C oracle by
 tests/test_pc_twin.py) bit for bit: iteration count, reason, residual norm, every history entry and x.  The
 operators have a variable diagonal and reach every MatMult route; the shapes are the smallest that reach each path
 of the kernels: a partial chunk only, odd n, one chunk plus a tail, two chunks plus a tail, more than 32 vectors,

@@ -1,4 +1,4 @@
-"""The left-Jacobi Arnoldi step (msplit_pcj.hip) one launcher at a time, on guarded work buffers.
+"""The left-Jacobi Arnoldi step (msplit_cgs_basis.hip) one launcher at a time, on guarded work buffers.
 
 ksp_gmres.c:enqueue_cycle drives a Jacobi cycle through mspi_pcj_apply_norm, mspi_pcj_mdot and
 mspi_pcj_maxpy_norm_update (msplit_internal.h).  This file binds the three by ctypes on the pattern of
@@ -7,9 +7,9 @@ msp_ksp_set_up lays them out, every non-operand word a NaN of a known bit patter
 bitwise the twin's arithmetic (tests/pc_twin.py) and every other word is unchanged -- the basis pads [n, stride), the
 raw W, dinv, the other vectors; with the stop flag set every launcher is a no-op.
 
-n = 4352 is one full chunk plus a tail, n = 1001 a partial chunk only with an odd n; m = 6 reaches the leading
-groups of 1, 2 and 3 vectors and the first group of four in both CGS kernels.  dinv lives in StepWork's "cur"
-region (the f64 step has no current vector).
+n = 4352 is one full chunk plus a tail, n = 1001 a partial chunk only with an odd n; m = 13 reaches the groups of
+1, 2 and 3 vectors before (MAXPY) and after (MDot) the groups of four, and takes the loop over groups of four up to
+three times in both CGS kernels.  dinv lives in StepWork's "cur" region (the f64 step has no current vector).
 """
 import ctypes as C
 
@@ -66,7 +66,7 @@ class Step:
 
 
 SHAPES = {4352: (17, 16, 16), 1001: (13, 11, 7)}
-M = 6
+M = 13
 
 
 @pytest.mark.parametrize("n", list(SHAPES))
