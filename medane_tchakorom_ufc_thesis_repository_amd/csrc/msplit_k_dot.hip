@@ -57,7 +57,7 @@ extern "C" int msk_dot_stage1(const double* w, const Vecs* V, int nv, int64_t n,
                   ((msk_tuning_flags & MSK_TUNE_MDOT_UNROLL2) ? 32 : 0);
   if (self)
     k_dot_stage1<1, true, 0><<<dim3((unsigned)nchunks), dim3(kT), 0, s>>>(w, *V, n, partial, nchunks, stop, 0);
-  else if (var == 1) dot1_dispatch<1, 1>(nv, w, *V, n, partial, nchunks, stop, s);
+  else if (var == 1) dot1_launch<1>(nv, w, *V, n, partial, nchunks, stop, s);
   else if (msk_dot1_variants_a(var, nv, w, *V, n, partial, nchunks, stop, s) &&
            msk_dot1_variants_b(var, nv, w, *V, n, partial, nchunks, stop, s))
     return (int)hipErrorInvalidValue;  // a tuning combination with no kernel: fail, never run another one
@@ -66,7 +66,8 @@ extern "C" int msk_dot_stage1(const double* w, const Vecs* V, int nv, int64_t n,
 
 extern "C" int msk_dot_stage2(const double* partial, int64_t nchunks, int nv, double* out, const int* stop,
                               hipStream_t s) {
-  if (stop) k_dot_stage2<true><<<dim3(nv), dim3(kT), 0, s>>>(partial, nchunks, out, stop);
-  else k_dot_stage2<false><<<dim3(nv), dim3(kT), 0, s>>>(partial, nchunks, out, nullptr);
+  pick<true, false>(stop != nullptr, [&](auto hs) {
+    k_dot_stage2<decltype(hs)::value><<<dim3(nv), dim3(kT), 0, s>>>(partial, nchunks, out, stop);
+  });
   return (int)hipGetLastError();
 }

@@ -8,8 +8,5 @@ using namespace msk;
 // Returns 0 when it launched the variant, 1 when the variant is not one of these.
 int msk_dot1_variants_a(int var, int nv, const double* w, const Vecs& V, int64_t n, double* partial,
                         int64_t nchunks, const int* stop, hipStream_t s) {
-  if (var == 0) dot1_dispatch<1, 0>(nv, w, V, n, partial, nchunks, stop, s);
-  else if (var == 16) dot1_dispatch<1, 16>(nv, w, V, n, partial, nchunks, stop, s);
-  else return 1;
-  return 0;
+  return pick<0, 16>(var, [&](auto v) { dot1_launch<decltype(v)::value>(nv, w, V, n, partial, nchunks, stop, s); }) ? 0 : 1;
 }

@@ -25,21 +25,15 @@ __global__ __launch_bounds__(kT) void k_dot_stage1_op(EllOp op, Vecs V, int64_t 
 // ===================================================================== launchers
 using namespace msk;
 
-template <int NV, int VAR>
-static void dot1_op_dispatch(int nv, const EllOp& op, const Vecs& V, int64_t n, double* partial, int64_t nchunks,
-                             const int* stop, hipStream_t s) {
-  if (nv == NV) {
-    k_dot_stage1_op<NV, VAR><<<dim3((unsigned)nchunks), dim3(kT), 0, s>>>(op, V, n, partial, nchunks, stop);
-  } else if constexpr (NV < MSK_MAX_GROUP) {
-    dot1_op_dispatch<NV + 1, VAR>(nv, op, V, n, partial, nchunks, stop, s);
-  }
-}
-
 extern "C" int msk_dot_stage1_op(const EllOp* op, const Vecs* V, int nv, int64_t n, double* partial,
                                  int64_t nchunks, const int* stop, hipStream_t s) {
   if (nchunks <= 0) return 0;
   if (nv < 1 || nv > MSK_MAX_GROUP || op->ndict > 255) return (int)hipErrorInvalidValue;
-  if (vec_var()) dot1_op_dispatch<1, 1>(nv, *op, *V, n, partial, nchunks, stop, s);
-  else dot1_op_dispatch<1, 0>(nv, *op, *V, n, partial, nchunks, stop, s);
+  pick<1, 0>(vec_var(), [&](auto var) {
+    pick_range<1, MSK_MAX_GROUP>(nv, [&](auto k) {
+      k_dot_stage1_op<decltype(k)::value, decltype(var)::value><<<dim3((unsigned)nchunks), dim3(kT), 0, s>>>(
+          *op, *V, n, partial, nchunks, stop);
+    });
+  });
   return (int)hipGetLastError();
 }

@@ -206,16 +206,18 @@ __global__ __launch_bounds__(kT) void k_maxpy_op(EllOp op, double* wout, Vecs V,
 // ===================================================================== launchers
 using namespace msk;
 
+// The bits of the MAXPY kernels' VAR.  VAR is a template argument and so part of every kernel's name: the values stay.
+enum { kVarNtLoad = 1, kVarNtStore = 4, kVarHalves = 8, kVarUnroll2 = 32, kVarTopFirst = 64 };
+
 extern "C" int msk_maxpy_op(const EllOp* op, double* wout, const Vecs* V, int nv, const double* adev, int64_t n,
                             double* partial, const int* stop, hipStream_t s) {
   if (n <= 0 || nv <= 0) return 0;
   if (op->ndict > 255) return (int)hipErrorInvalidValue;
   const unsigned g = (unsigned)((n + kChunk - 1) / kChunk);
-  const int var = vec_var() | ((msk_tuning_flags & MSK_TUNE_MAXPY_TEMPORAL_ST) ? 0 : 4);
-  if (var == 5) k_maxpy_op<5><<<g, kT, 0, s>>>(*op, wout, *V, adev, nv, n, partial, stop);
-  else if (var == 4) k_maxpy_op<4><<<g, kT, 0, s>>>(*op, wout, *V, adev, nv, n, partial, stop);
-  else if (var == 1) k_maxpy_op<1><<<g, kT, 0, s>>>(*op, wout, *V, adev, nv, n, partial, stop);
-  else k_maxpy_op<0><<<g, kT, 0, s>>>(*op, wout, *V, adev, nv, n, partial, stop);
+  const int var = vec_var() | ((msk_tuning_flags & MSK_TUNE_MAXPY_TEMPORAL_ST) ? 0 : kVarNtStore);
+  pick<5, 4, 1, 0>(var, [&](auto v) {
+    k_maxpy_op<decltype(v)::value><<<g, kT, 0, s>>>(*op, wout, *V, adev, nv, n, partial, stop);
+  });
   return (int)hipGetLastError();
 }
 
@@ -225,41 +227,27 @@ extern "C" int msk_maxpy_chunk(const double* win, double* wout, const Vecs* V, i
   if (n <= 0 || (nv <= 0 && !nvdev)) return 0;
   // non-temporal store of w too unless MSK_TUNE_MAXPY_TEMPORAL_ST (+0.4 % per step); the group loop
   // unrolled by two unless MSK_TUNE_MAXPY_UNROLL1 (+1.7 % per step: 64-load bursts at one wave per SIMD)
-  const int var = vec_var() | ((msk_tuning_flags & MSK_TUNE_MAXPY_TEMPORAL_ST) ? 0 : 4) |
-                  ((msk_tuning_flags & MSK_TUNE_MAXPY_HALVES) ? 8 : 0) | ((msk_tuning_flags & MSK_TUNE_MAXPY_UNROLL1) ? 0 : 32);
+  int var = vec_var() | ((msk_tuning_flags & MSK_TUNE_MAXPY_TEMPORAL_ST) ? 0 : kVarNtStore) |
+            ((msk_tuning_flags & MSK_TUNE_MAXPY_HALVES) ? kVarHalves : 0) |
+            ((msk_tuning_flags & MSK_TUNE_MAXPY_UNROLL1) ? 0 : kVarUnroll2);
   // Top chunk first where a vector outgrows the 256 MiB MALL (n > 2^25): MAXPY then starts on the rows the
   // fused MatMult+MDot (or the MDot) left in the MALL and ends on those the next one starts with (SMSM's
   // 512x512x256 block +1.0 %, MAXPY 5.68 -> 5.86 TB/s; at 256^3, where whole vectors fit, -0.7 %; same box,
-  // profiles/r03/rev_ab/).  MSPLIT_MAXPY_REV=0/1 forces either order.
-  static const int rev_env = [] {
-    const char* e = getenv("MSPLIT_MAXPY_REV");
-    return e ? (atoi(e) ? 1 : 0) : -1;
-  }();
-  const int rev = (rev_env < 0 ? n > ((int64_t)1 << 25) : rev_env) ? 64 : 0;
+  // profiles/r03/rev_ab/).  MSPLIT_MAXPY_REV=0/1 forces either order (maxpy_rev).  Only the two variants with
+  // non-temporal loads and the unrolled group loop (33, 37) have the reversed form (97, 101).
+  if (maxpy_rev(n) && (var == 33 || var == 37)) var |= kVarTopFirst;
   const unsigned g = (unsigned)((n + kChunk - 1) / kChunk);
-#define MSK_MAXPY_LAUNCH(V_)                                                                                     \
-  if (partial)                                                                                                  \
-    k_maxpy_chunk<false, true, V_><<<dim3(g), dim3(kT), 0, s>>>(win, wout, *V, *A, adev, negate, nv, nvdev, n,   \
-                                                                partial, stop);                                \
-  else if (accum)                                                                                               \
-    k_maxpy_chunk<true, false, V_><<<dim3(g), dim3(kT), 0, s>>>(win, wout, *V, *A, adev, negate, nv, nvdev, n,   \
-                                                                partial, stop);                                \
-  else                                                                                                          \
-    k_maxpy_chunk<false, false, V_><<<dim3(g), dim3(kT), 0, s>>>(win, wout, *V, *A, adev, negate, nv, nvdev, n,  \
-                                                                 partial, stop);
-  switch (var) {
-    case 0: MSK_MAXPY_LAUNCH(0) break;
-    case 1: MSK_MAXPY_LAUNCH(1) break;
-    case 4: MSK_MAXPY_LAUNCH(4) break;
-    case 5: MSK_MAXPY_LAUNCH(5) break;
-    case 13: MSK_MAXPY_LAUNCH(13) break;
-    case 32: MSK_MAXPY_LAUNCH(32) break;
-    case 33: if (rev) { MSK_MAXPY_LAUNCH(97) } else { MSK_MAXPY_LAUNCH(33) } break;
-    case 36: MSK_MAXPY_LAUNCH(36) break;
-    case 37: if (rev) { MSK_MAXPY_LAUNCH(101) } else { MSK_MAXPY_LAUNCH(37) } break;
-    case 45: MSK_MAXPY_LAUNCH(45) break;
-    default: return (int)hipErrorInvalidValue;  // a tuning combination with no kernel: fail, never run another one
-  }
-#undef MSK_MAXPY_LAUNCH
+  const bool known = pick<0, 1, 4, 5, 13, 32, 33, 36, 37, 45, 97, 101>(var, [&](auto v) {
+    constexpr int VAR = decltype(v)::value;
+    if (partial)  // with the ||w||^2 partials
+      k_maxpy_chunk<false, true, VAR><<<dim3(g), dim3(kT), 0, s>>>(win, wout, *V, *A, adev, negate, nv, nvdev, n, partial,
+                                                                   stop);
+    else
+      pick<true, false>(accum != 0, [&](auto acc) {
+        k_maxpy_chunk<decltype(acc)::value, false, VAR><<<dim3(g), dim3(kT), 0, s>>>(win, wout, *V, *A, adev, negate, nv,
+                                                                                   nvdev, n, partial, stop);
+      });
+  });
+  if (!known) return (int)hipErrorInvalidValue;  // a tuning combination with no kernel: fail, never run another one
   return (int)hipGetLastError();
 }

@@ -141,17 +141,6 @@ __global__ __launch_bounds__(kT) void k_maxpy_mdot(const double* __restrict__ wi
   if (t <= NV) partial[t * nchunks + c] = (red[t][0] + red[t][1]) + (red[t][2] + red[t][3]);
 }
 
-template <int NV, int VAR>
-void maxpy_mdot_dispatch(int nv, const double* win, double* wout, const Vecs& V, const double* adev, int64_t n,
-                         double* partial, int64_t nchunks, int rev, const int* stop, hipStream_t s) {
-  if (nv == NV) {
-    k_maxpy_mdot<NV, VAR><<<dim3((unsigned)nchunks), dim3(kT), 0, s>>>(win, wout, V, adev, n, partial, nchunks, rev,
-                                                                       stop);
-  } else if constexpr (NV + 1 < MSK_MAX_GROUP) {
-    maxpy_mdot_dispatch<NV + 1, VAR>(nv, win, wout, V, adev, n, partial, nchunks, rev, stop, s);
-  }
-}
-
 }  // namespace
 }  // namespace msk
 
@@ -164,9 +153,11 @@ extern "C" int msk_maxpy_mdot(const double* win, double* wout, const Vecs* V, in
   if (nv < 1 || nv + 1 > MSK_MAX_GROUP) return (int)hipErrorInvalidValue;  // partial has MSK_MAX_GROUP rows
   const int rev = n > ((int64_t)1 << 25);  // msk_maxpy_chunk's rule
   // the store policy follows MSK_TUNE_MAXPY_TEMPORAL_ST; the basis loads are non-temporal
-  if (msk_tuning_flags & MSK_TUNE_MAXPY_TEMPORAL_ST)
-    maxpy_mdot_dispatch<1, 1>(nv, win, wout, *V, adev, n, partial, nchunks, rev, stop, s);
-  else
-    maxpy_mdot_dispatch<1, 5>(nv, win, wout, *V, adev, n, partial, nchunks, rev, stop, s);
+  pick<1, 5>((msk_tuning_flags & MSK_TUNE_MAXPY_TEMPORAL_ST) ? 1 : 5, [&](auto var) {
+    pick_range<1, MSK_MAX_GROUP - 1>(nv, [&](auto k) {
+      k_maxpy_mdot<decltype(k)::value, decltype(var)::value><<<dim3((unsigned)nchunks), dim3(kT), 0, s>>>(
+          win, wout, *V, adev, n, partial, nchunks, rev, stop);
+    });
+  });
   return (int)hipGetLastError();
 }

@@ -1,15 +1,19 @@
 // msplit_kdev.hpp -- what more than one of the kernel units of the GMRES inner-solve path (msplit_k_*.hip,
 // msplit_kernels.hip) needs: the DBR constants, the small device helpers, the MDot chunk bodies and MAXPY's
 // group sum (the dot and MAXPY kernels and the kernels that fuse a MatMult with them) and, for the launchers,
-// the tuning flags and the MDot stage-1 dispatch (with the kernel template k_dot_stage1, which three units
-// instantiate).  Private to those units: not installed and not included anywhere else.  A helper that one unit
-// uses lives in that unit.
+// the tuning flags, the dispatch helper that turns a run-time value into a template argument (pick, pick_range), the
+// reader of the environment knobs (env_int) and the MDot stage-1 launch (with the kernel template k_dot_stage1,
+// which three units instantiate).  Private to those units: not installed and not included anywhere else.  A helper
+// that one unit uses lives in that unit.  tools/launch_table.cpp prints what every launcher of these units picks,
+// without a GPU.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdint>
+#include <cstdlib>
+#include <type_traits>
 
 #include "msplit_kernels.h"
 
@@ -327,21 +331,55 @@ __attribute__((visibility("hidden"))) int msk_dot1_variants_b(int var, int nv, c
 namespace msk {
 namespace {
 
+// A run-time value as a template argument: pick<V0, Vs...>(v, f) calls f(std::integral_constant<.., V>{}) for the
+// listed V that equals v and returns whether one did; pick_range<LO, HI> lists LO..HI.  f is a generic lambda that
+// launches the kernel with decltype(c)::value as the argument.  Only the listed values are instantiated, so a launcher
+// lists exactly the kernels that exist, and a value that is not listed launches nothing.
+template <auto V0, auto... Vs, class T, class F>
+inline bool pick(T v, F&& f) {
+  if (v == (T)V0) {
+    f(std::integral_constant<decltype(V0), V0>{});
+    return true;
+  }
+  if constexpr (sizeof...(Vs) > 0) return pick<Vs...>(v, f);
+  else return false;
+}
+template <int LO, int HI, class F>
+inline bool pick_range(int v, F&& f) {
+  if (v == LO) {
+    f(std::integral_constant<int, LO>{});
+    return true;
+  }
+  if constexpr (LO < HI) return pick_range<LO + 1, HI>(v, f);
+  else return false;
+}
+
+// An integer knob of the environment: atoi of its value, dflt where it is not set.
+inline int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+
 // basis-vector load policy: non-temporal unless MSK_TUNE_VEC_TEMPORAL (A/B)
 inline int vec_var() { return (msk_tuning_flags & MSK_TUNE_VEC_TEMPORAL) ? 0 : 1; }
 
+// MAXPY's chunk order (msk_maxpy_chunk, msk_box_maxpy_march): top chunks first where a vector outgrows the 256 MiB
+// MALL (n > 2^25); MSPLIT_MAXPY_REV=0/1 forces either order.
+inline bool maxpy_rev(int64_t n) {
+  static const int forced = getenv("MSPLIT_MAXPY_REV") ? (env_int("MSPLIT_MAXPY_REV", 0) ? 1 : 0) : -1;
+  return forced < 0 ? n > ((int64_t)1 << 25) : forced != 0;
+}
+
 // MDot stage 1 is launched from three units (msplit_k_dot.hip: the default variant; msplit_k_dot_a.hip and
-// msplit_k_dot_b.hip: the A/B variants), so the kernel template k_dot_stage1 and this dispatch are here and each of
-// the three instantiates its own variants.
-template <int NV, int VAR>
-void dot1_dispatch(int nv, const double* w, const Vecs& V, int64_t n, double* partial, int64_t nchunks,
-                          const int* stop, hipStream_t s) {
-  if (nv == NV) {
-    k_dot_stage1<NV, false, VAR><<<dim3((unsigned)nchunks), dim3(kT), 0, s>>>(
+// msplit_k_dot_b.hip: the A/B variants), so the kernel template k_dot_stage1 and this launch are here and each of
+// the three instantiates its own variants.  False when nv is not in 1..MSK_MAX_GROUP.
+template <int VAR>
+bool dot1_launch(int nv, const double* w, const Vecs& V, int64_t n, double* partial, int64_t nchunks, const int* stop,
+                 hipStream_t s) {
+  return pick_range<1, MSK_MAX_GROUP>(nv, [&](auto k) {
+    k_dot_stage1<decltype(k)::value, false, VAR><<<dim3((unsigned)nchunks), dim3(kT), 0, s>>>(
         w, V, n, partial, nchunks, stop, (msk_tuning_flags & MSK_TUNE_MDOT_REV) ? 1 : 0);
-  } else if constexpr (NV < MSK_MAX_GROUP) {
-    dot1_dispatch<NV + 1, VAR>(nv, w, V, n, partial, nchunks, stop, s);
-  }
+  });
 }
 
 }  // namespace

@@ -2532,10 +2532,7 @@ extern "C" void msk_set_march_lines(int l) {
 extern "C" int msk_get_shape_epoch(void) { return msk_shape_epoch; }
 // The W-free GMRES step for box stencils (k_box_maxpy_march recomputes W; the fused MatMult+MDot does not store
 // it): on unless MSPLIT_GM_WFREE=0; msk_set_gm_wfree switches it (A/B, tests) and re-keys captured cycles.
-__attribute__((visibility("hidden"))) int msk_gm_wfree = [] {
-  const char* e = getenv("MSPLIT_GM_WFREE");
-  return e ? (atoi(e) ? 1 : 0) : 1;
-}();
+__attribute__((visibility("hidden"))) int msk_gm_wfree = env_int("MSPLIT_GM_WFREE", 1) ? 1 : 0;
 extern "C" void msk_set_gm_wfree(int on) {
   msk_gm_wfree = on ? 1 : 0;
   ++msk_shape_epoch;
@@ -2548,8 +2545,7 @@ extern "C" int msk_get_gm_wfree(void) { return msk_gm_wfree; }
 // cycles.  Every setting gives the same bits.
 constexpr int kMaxpyPrefetchDefault = 1;
 __attribute__((visibility("hidden"))) int msk_maxpy_prefetch = [] {
-  const char* e = getenv("MSPLIT_MAXPY_PREFETCH");
-  const int v = e ? atoi(e) : kMaxpyPrefetchDefault;
+  const int v = env_int("MSPLIT_MAXPY_PREFETCH", kMaxpyPrefetchDefault);
   return v < 0 || v > 3 ? kMaxpyPrefetchDefault : v;
 }();
 extern "C" void msk_set_maxpy_prefetch(int mode) {
@@ -2593,6 +2589,12 @@ static inline int grid_for(int64_t work, int cap) {
   return (int)g;
 }
 
+// The SpMV mode as a template argument: f(RESID), f(SCALED), and f(MULT) for every other value.
+template <class F>
+static void pick_mode(int mode, F&& f) {
+  if (!pick<(int)MSK_SPMV_RESID, (int)MSK_SPMV_SCALED>(mode, f)) f(std::integral_constant<int, MSK_SPMV_MULT>{});
+}
+
 extern "C" int msk_spmv(int32_t nrows, const int32_t* rowptr, const int32_t* col, const double* val, const double* x,
                         const double* b, double* y, int32_t lds_cap, int mode, const double* sdev, double* vout,
                         const int* stop, int64_t plane, hipStream_t s) {
@@ -2607,57 +2609,25 @@ extern "C" int msk_spmv(int32_t nrows, const int32_t* rowptr, const int32_t* col
     const bool glds = !reg && !stage1;
     // a combination with no kernel fails instead of running another variant
     if ((tmp && nty) || (reg && stage1)) return (int)hipErrorInvalidValue;
-    const bool nt = !tmp && !nty;
-    const bool ntst = !tmp;
+    // the load / store policy: 3 = non-temporal col/val loads and y stores, 2 = y stores only, 0 = neither
+    const int pol = !tmp && !nty ? 3 : !tmp ? 2 : 0;
+    const int stage = glds ? 0 : stage1 ? 1 : 4;
     const int32_t cap = glds ? ((lds_cap + 255) & ~255) : lds_cap;
     const size_t ldsb = (size_t)cap * 12;  // LDS-DMA: slack for the last instruction's tail lanes
-#define LAUNCH_LDS8(M, POL_)                                                                                  \
-  do {                                                                                                         \
-    if (glds)                                                                                                  \
-      k_spmv_lds8<M, POL_, 0><<<dim3(g), dim3(kT), ldsb, s>>>(nrows, rowptr, col, val, x, b, y, cap, sdev,     \
-                                                               vout, stop, xm);                                \
-    else if (stage1)                                                                                           \
-      k_spmv_lds8<M, POL_, 1><<<dim3(g), dim3(kT), ldsb, s>>>(nrows, rowptr, col, val, x, b, y, cap, sdev,     \
-                                                               vout, stop, xm);                                \
-    else                                                                                                       \
-      k_spmv_lds8<M, POL_, 4><<<dim3(g), dim3(kT), ldsb, s>>>(nrows, rowptr, col, val, x, b, y, cap, sdev,     \
-                                                               vout, stop, xm);                                \
-  } while (0)
-#define LAUNCH_POL(M)                            \
-  do {                                           \
-    if (nt) LAUNCH_LDS8(M, 3);                   \
-    else if (ntst) LAUNCH_LDS8(M, 2);            \
-    else LAUNCH_LDS8(M, 0);                      \
-  } while (0)
-    if (mode == MSK_SPMV_RESID) LAUNCH_POL(MSK_SPMV_RESID);
-    else if (mode == MSK_SPMV_SCALED) LAUNCH_POL(MSK_SPMV_SCALED);
-    else LAUNCH_POL(MSK_SPMV_MULT);
-#undef LAUNCH_POL
-#undef LAUNCH_LDS8
+    pick_mode(mode, [&](auto m) {
+      pick<3, 2, 0>(pol, [&](auto p) {
+        pick<0, 1, 4>(stage, [&](auto st) {
+          k_spmv_lds8<decltype(m)::value, decltype(p)::value, decltype(st)::value><<<dim3(g), dim3(kT), ldsb, s>>>(
+              nrows, rowptr, col, val, x, b, y, cap, sdev, vout, stop, xm);
+        });
+      });
+    });
   } else {
-    if (mode == MSK_SPMV_RESID)
-      k_spmv_direct<MSK_SPMV_RESID><<<dim3(g), dim3(kT), 0, s>>>(nrows, rowptr, col, val, x, b, y, sdev, vout, stop);
-    else if (mode == MSK_SPMV_SCALED)
-      k_spmv_direct<MSK_SPMV_SCALED><<<dim3(g), dim3(kT), 0, s>>>(nrows, rowptr, col, val, x, b, y, sdev, vout, stop);
-    else
-      k_spmv_direct<MSK_SPMV_MULT><<<dim3(g), dim3(kT), 0, s>>>(nrows, rowptr, col, val, x, b, y, sdev, vout, stop);
+    pick_mode(mode, [&](auto m) {
+      k_spmv_direct<decltype(m)::value><<<dim3(g), dim3(kT), 0, s>>>(nrows, rowptr, col, val, x, b, y, sdev, vout, stop);
+    });
   }
   return (int)hipGetLastError();
-}
-
-template <int W, int RPL, bool NTY>
-static void launch_ell_pol(int mode, unsigned g, int32_t nrows, const uint8_t* code8, const int32_t* ddelta,
-                           const double* dval, int ndict, const double* x, const double* b, double* y,
-                           const double* sdev, double* vout, const int* stop, int32_t xwin, hipStream_t s) {
-  if (mode == MSK_SPMV_RESID)
-    k_spmv_ell<MSK_SPMV_RESID, W, RPL, NTY><<<g, kT, 0, s>>>(nrows, code8, ddelta, dval, ndict, x, b, y, sdev, vout,
-                                                             stop, xwin);
-  else if (mode == MSK_SPMV_SCALED)
-    k_spmv_ell<MSK_SPMV_SCALED, W, RPL, NTY><<<g, kT, 0, s>>>(nrows, code8, ddelta, dval, ndict, x, b, y, sdev, vout,
-                                                              stop, xwin);
-  else
-    k_spmv_ell<MSK_SPMV_MULT, W, RPL, NTY><<<g, kT, 0, s>>>(nrows, code8, ddelta, dval, ndict, x, b, y, sdev, vout,
-                                                            stop, xwin);
 }
 
 template <int W, int RPL>
@@ -2667,10 +2637,13 @@ static void launch_ell(int mode, int32_t nrows, const uint8_t* code8, const int3
   const unsigned g = (unsigned)((nrows + kT * RPL - 1) / (kT * RPL));
   const bool xon = (msk_tuning_flags & MSK_TUNE_ELL_XCD_ON) || (plane >= (1 << 18) && !(msk_tuning_flags & MSK_TUNE_ELL_XCD_OFF));
   const int32_t xwin = xon ? 8 : 0;
-  if (!(msk_tuning_flags & MSK_TUNE_ELL_TEMPORAL_Y))  // default: non-temporal y (GMRES step +1.1 %, profiles/r02/nt_ab/)
-    launch_ell_pol<W, RPL, true>(mode, g, nrows, code8, ddelta, dval, ndict, x, b, y, sdev, vout, stop, xwin, s);
-  else
-    launch_ell_pol<W, RPL, false>(mode, g, nrows, code8, ddelta, dval, ndict, x, b, y, sdev, vout, stop, xwin, s);
+  // default: non-temporal y (GMRES step +1.1 %, profiles/r02/nt_ab/)
+  pick<true, false>(!(msk_tuning_flags & MSK_TUNE_ELL_TEMPORAL_Y), [&](auto nty) {
+    pick_mode(mode, [&](auto m) {
+      k_spmv_ell<decltype(m)::value, W, RPL, decltype(nty)::value><<<g, kT, 0, s>>>(nrows, code8, ddelta, dval, ndict, x, b,
+                                                                                  y, sdev, vout, stop, xwin);
+    });
+  });
 }
 
 // DV SpMV flag pairs that name no kernel: an error on every DV path, whichever kernel the operator takes
@@ -2685,17 +2658,13 @@ template <bool NTY, int L, bool D2>
 static void launch_box_march(int mode, unsigned g, int32_t nx, int32_t ny, int32_t nz, const uint8_t* mask,
                              const double* dval, const double* x, const double* b, double* y, const double* sdev,
                              double* vout, const int* stop, int32_t zt, int32_t xwin, hipStream_t s) {
-#define MSK_BM(M)                                                                                                 \
-  do {                                                                                                            \
-    if constexpr (L == 0)                                                                                         \
-      k_spmv_box_march<M, NTY, D2><<<g, kT, 0, s>>>(nx, ny, nz, mask, dval, x, b, y, sdev, vout, stop, zt, xwin);    \
-    else                                                                                                          \
-      k_spmv_box_lines<M, NTY, L><<<g, kT, 0, s>>>(nx, ny, nz, mask, dval, x, b, y, sdev, vout, stop, zt, xwin); \
-  } while (0)
-  if (mode == MSK_SPMV_RESID) MSK_BM(MSK_SPMV_RESID);
-  else if (mode == MSK_SPMV_SCALED) MSK_BM(MSK_SPMV_SCALED);
-  else MSK_BM(MSK_SPMV_MULT);
-#undef MSK_BM
+  pick_mode(mode, [&](auto m) {
+    constexpr int M = decltype(m)::value;
+    if constexpr (L == 0)
+      k_spmv_box_march<M, NTY, D2><<<g, kT, 0, s>>>(nx, ny, nz, mask, dval, x, b, y, sdev, vout, stop, zt, xwin);
+    else
+      k_spmv_box_lines<M, NTY, L><<<g, kT, 0, s>>>(nx, ny, nz, mask, dval, x, b, y, sdev, vout, stop, zt, xwin);
+  });
 }
 
 // Kernel and shape: nx % 256 == 0 takes tiles of 4 lines (k_spmv_box_lines) when 16 planes per workgroup,
@@ -2734,6 +2703,16 @@ static bool march_chunk_ok(int32_t nx, int32_t ny, int d2) {
   return !d2 && P % kChunk == 0 && (nx & 1) == 0 && nx >= 2 && nx <= 2048;
 }
 
+// The kernels' RV argument: 0 = the dictionary's seven values, 1 = each row's own values (rv[e * rvs + row]),
+// 2 = the symmetric storage (rvs < 0)
+static int rv_form(const double* rv, int64_t rvs) { return !rv ? 0 : rvs < 0 ? 2 : 1; }
+
+// MSPLIT_MARCH_CHUNK=0 turns the chunk-tile march off (msk_spmv_box_march, msk_march_chunk_fits)
+static int march_chunk_env() {
+  static const int v = env_int("MSPLIT_MARCH_CHUNK", 1);
+  return v;
+}
+
 // The chunk-tile march launch (k_box_march_chunk) for a box whose planes hold whole DBR chunks; halo bit 0/1:
 // the column space has the plane below / above the box (x points at the box's first row).
 static int launch_march_chunk(int32_t nx, int32_t ny, int32_t nz, int halo, const uint8_t* mask, const double* dval,
@@ -2751,20 +2730,16 @@ static int launch_march_chunk(int32_t nx, int32_t ny, int32_t nz, int halo, cons
   const int xcd = cpp % 8 == 0 && cpp >= 32 && !(msk_tuning_flags & MSK_TUNE_ELL_MARCH_NOXCD);
   const bool nty = !(msk_tuning_flags & MSK_TUNE_ELL_TEMPORAL_Y);
   const size_t lds = (size_t)(kChunk + 2 * nx + (rv && rvs < 0 ? 2 * (kChunk + nx) : 0)) * sizeof(double);
-#define MSK_BMC(M, NT_, RV_)                                                                                    \
-  k_box_march_chunk<M, NT_, RV_><<<dim3((unsigned)grid), dim3(kT), lds, s>>>(nx, P, nz, zt, xcd, halo, mask, dval, rv, \
-                                                                             rvs, x, b, y, sdev, vout, stop)
-#define MSK_BMC2(M)                                                           \
-  do {                                                                        \
-    if (rv && rvs < 0) { if (nty) MSK_BMC(M, true, 2); else MSK_BMC(M, false, 2); } \
-    else if (rv) { if (nty) MSK_BMC(M, true, 1); else MSK_BMC(M, false, 1); }          \
-    else { if (nty) MSK_BMC(M, true, 0); else MSK_BMC(M, false, 0); }                  \
-  } while (0)
-  if (mode == MSK_SPMV_RESID) MSK_BMC2(MSK_SPMV_RESID);
-  else if (mode == MSK_SPMV_SCALED) MSK_BMC2(MSK_SPMV_SCALED);
-  else MSK_BMC2(MSK_SPMV_MULT);
-#undef MSK_BMC2
-#undef MSK_BMC
+  const int form = rv_form(rv, rvs);
+  pick_mode(mode, [&](auto m) {
+    pick<true, false>(nty, [&](auto nt) {
+      pick<0, 1, 2>(form, [&](auto f) {
+        k_box_march_chunk<decltype(m)::value, decltype(nt)::value, decltype(f)::value>
+            <<<dim3((unsigned)grid), dim3(kT), lds, s>>>(nx, P, nz, zt, xcd, halo, mask, dval, rv, rvs, x, b, y, sdev, vout,
+                                                         stop);
+      });
+    });
+  });
   return (int)hipGetLastError();
 }
 
@@ -2777,15 +2752,11 @@ extern "C" int msk_spmv_box_march(int32_t nx, int32_t ny, int32_t nz, int d2, co
     return (int)hipErrorInvalidValue;
   if (msk_march_lines_override == 4 && nx % kT) return (int)hipErrorInvalidValue;
   if (d2 && msk_march_lines_override == 4) return (int)hipErrorInvalidValue;
-  static const int chunk_env = [] {
-    const char* e = getenv("MSPLIT_MARCH_CHUNK");
-    return e ? atoi(e) : 1;
-  }();
   auto a16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
   const bool chunk_ok = march_chunk_ok(nx, ny, d2) && a16(x) && a16(y) &&
                         (mode != MSK_SPMV_RESID || a16(b)) && (mode != MSK_SPMV_SCALED || !vout || a16(vout));
   if (msk_march_lines_override == 16 && !chunk_ok) return (int)hipErrorInvalidValue;
-  if (chunk_ok && (msk_march_lines_override == 16 || (msk_march_lines_override == 0 && chunk_env != 0)))
+  if (chunk_ok && (msk_march_lines_override == 16 || (msk_march_lines_override == 0 && march_chunk_env() != 0)))
     return launch_march_chunk(nx, ny, nz, 0, mask, dval, x, b, y, mode, sdev, vout, stop, s);
   int32_t L, zt;
   int64_t g;
@@ -2793,29 +2764,20 @@ extern "C" int msk_spmv_box_march(int32_t nx, int32_t ny, int32_t nz, int d2, co
   if (g > INT32_MAX || (int64_t)nx * ny * nz > INT32_MAX) return (int)hipErrorInvalidValue;
   const int32_t xwin = (msk_tuning_flags & MSK_TUNE_ELL_MARCH_NOXCD) ? 0 : 32;
   const bool nty = !(msk_tuning_flags & MSK_TUNE_ELL_TEMPORAL_Y);
-#define MSK_BML(NT, LL, D) \
-  launch_box_march<NT, LL, D>(mode, (unsigned)g, nx, ny, nz, mask, dval, x, b, y, sdev, vout, stop, zt, xwin, s)
-  if (d2) {
-    if (nty) MSK_BML(true, 0, true);
-    else MSK_BML(false, 0, true);
-  } else if (L == 4) {
-    if (nty) MSK_BML(true, 4, false);
-    else MSK_BML(false, 4, false);
-  } else {
-    if (nty) MSK_BML(true, 0, false);
-    else MSK_BML(false, 0, false);
-  }
-#undef MSK_BML
+  const int form = d2 ? 2 : L == 4 ? 1 : 0;  // the three forms that exist: the 3D march, tiles of four lines, the 2D march
+  pick<true, false>(nty, [&](auto nt) {
+    pick<0, 1, 2>(form, [&](auto f) {
+      constexpr int F = decltype(f)::value;
+      launch_box_march<decltype(nt)::value, F == 1 ? 4 : 0, F == 2>(mode, (unsigned)g, nx, ny, nz, mask, dval, x, b, y, sdev,
+                                                                   vout, stop, zt, xwin, s);
+    });
+  });
   return (int)hipGetLastError();
 }
 
 // Whether the chunk-tile march takes a box of nx x ny planes (and MSPLIT_MARCH_CHUNK does not turn it off).
 extern "C" int msk_march_chunk_fits(int32_t nx, int32_t ny, int d2) {
-  static const int chunk_env = [] {
-    const char* e = getenv("MSPLIT_MARCH_CHUNK");
-    return e ? atoi(e) : 1;
-  }();
-  return chunk_env != 0 && march_chunk_ok(nx, ny, d2);
+  return march_chunk_env() != 0 && march_chunk_ok(nx, ny, d2);
 }
 
 // MatMult / MatResidual of a box stencil whose column space adds the plane below (halo & 1) and / or above
@@ -2858,8 +2820,7 @@ extern "C" int msk_box_march_chunk_rv(int32_t nx, int32_t ny, int32_t nz, const 
 extern "C" int msk_march_mask(int32_t nrows, int d2, const uint8_t* code8, uint8_t* mask, hipStream_t s) {
   if (nrows <= 0) return 0;
   const unsigned g = (unsigned)((nrows + kT - 1) / kT);
-  if (d2) k_march_mask<true><<<g, kT, 0, s>>>(nrows, code8, mask);
-  else k_march_mask<false><<<g, kT, 0, s>>>(nrows, code8, mask);
+  pick<true, false>(d2 != 0, [&](auto d) { k_march_mask<decltype(d)::value><<<g, kT, 0, s>>>(nrows, code8, mask); });
   return (int)hipGetLastError();
 }
 
@@ -2881,12 +2842,15 @@ extern "C" int msk_spmv_dv(int32_t nrows, const int32_t* rowptr, const uint8_t* 
   if (ell_w) {
     if (ndict > 255) return (int)hipErrorInvalidValue;
     const int rpl = (msk_tuning_flags & MSK_TUNE_DV_RPL1) ? 1 : (msk_tuning_flags & MSK_TUNE_DV_RPL2) ? 2 : (ell_w == 16 ? 2 : 4);
-#define MSK_ELL(W_, R_) launch_ell<W_, R_>(mode, nrows, code8, ddelta, dval, ndict, x, b, y, sdev, vout, stop, plane, s)
-    if (ell_w == 4) { if (rpl == 1) MSK_ELL(4, 1); else if (rpl == 2) MSK_ELL(4, 2); else MSK_ELL(4, 4); }
-    else if (ell_w == 8) { if (rpl == 1) MSK_ELL(8, 1); else if (rpl == 2) MSK_ELL(8, 2); else MSK_ELL(8, 4); }
-    else if (ell_w == 16) { if (rpl == 1) MSK_ELL(16, 1); else MSK_ELL(16, 2); }
-    else return (int)hipErrorInvalidValue;
-#undef MSK_ELL
+    const bool known = pick<4, 8, 16>(ell_w, [&](auto w) {
+      constexpr int W = decltype(w)::value;
+      auto go = [&](auto r) {
+        launch_ell<W, decltype(r)::value>(mode, nrows, code8, ddelta, dval, ndict, x, b, y, sdev, vout, stop, plane, s);
+      };
+      if constexpr (W == 16) pick<1, 2>(rpl, go);  // no four rows per lane at 16 codes per row
+      else pick<1, 2, 4>(rpl, go);
+    });
+    if (!known) return (int)hipErrorInvalidValue;
     return (int)hipGetLastError();
   }
   const int rpl = (msk_tuning_flags & MSK_TUNE_DV_RPL1) ? 1 : (msk_tuning_flags & MSK_TUNE_DV_RPL2) ? 2 : 4;
@@ -2895,29 +2859,19 @@ extern "C" int msk_spmv_dv(int32_t nrows, const int32_t* rowptr, const uint8_t* 
   if (rpl == 1) {
     const unsigned g = (unsigned)((nrows + kT - 1) / kT);
     const XcdMap xm = xcd_map(nrows, plane);
-#define MSK_DV(M) \
-  k_spmv_dv<M><<<dim3(g), dim3(kT), cap, s>>>(nrows, rowptr, len8, code8, ddelta, dval, ndict, x, b, y, sdev, vout, \
-                                              stop, xm)
-    if (mode == MSK_SPMV_RESID) MSK_DV(MSK_SPMV_RESID);
-    else if (mode == MSK_SPMV_SCALED) MSK_DV(MSK_SPMV_SCALED);
-    else MSK_DV(MSK_SPMV_MULT);
-#undef MSK_DV
+    pick_mode(mode, [&](auto m) {
+      k_spmv_dv<decltype(m)::value><<<dim3(g), dim3(kT), cap, s>>>(nrows, rowptr, len8, code8, ddelta, dval, ndict, x, b, y,
+                                                                   sdev, vout, stop, xm);
+    });
     return (int)hipGetLastError();
   }
   const unsigned g = (unsigned)((nrows + kT * rpl - 1) / (kT * rpl));
-#define MSK_DVB(M, R) \
-  k_spmv_dvb<M, R><<<dim3(g), dim3(kT), cap, s>>>(nrows, rowptr, len8, code8, ddelta, dval, ndict, x, b, y, sdev, \
-                                                  vout, stop)
-  if (rpl == 2) {
-    if (mode == MSK_SPMV_RESID) MSK_DVB(MSK_SPMV_RESID, 2);
-    else if (mode == MSK_SPMV_SCALED) MSK_DVB(MSK_SPMV_SCALED, 2);
-    else MSK_DVB(MSK_SPMV_MULT, 2);
-  } else {
-    if (mode == MSK_SPMV_RESID) MSK_DVB(MSK_SPMV_RESID, 4);
-    else if (mode == MSK_SPMV_SCALED) MSK_DVB(MSK_SPMV_SCALED, 4);
-    else MSK_DVB(MSK_SPMV_MULT, 4);
-  }
-#undef MSK_DVB
+  pick<2, 4>(rpl, [&](auto r) {
+    pick_mode(mode, [&](auto m) {
+      k_spmv_dvb<decltype(m)::value, decltype(r)::value><<<dim3(g), dim3(kT), cap, s>>>(
+          nrows, rowptr, len8, code8, ddelta, dval, ndict, x, b, y, sdev, vout, stop);
+    });
+  });
   return (int)hipGetLastError();
 }
 
@@ -2926,11 +2880,10 @@ static int spmm_ell_launch(int32_t nrows, int W, const uint8_t* code8, const int
                            int ndict, const double* S, int64_t lds, int nc, TR* R, int64_t ldr, hipStream_t s) {
   if (nrows <= 0 || nc <= 0) return 0;
   const unsigned g = (unsigned)((nrows + kT - 1) / kT);
-  if (W == 4) k_spmm_ell<4, TR><<<g, kT, 0, s>>>(nrows, code8, ddelta, dval, ndict, S, lds, nc, R, ldr);
-  else if (W == 8) k_spmm_ell<8, TR><<<g, kT, 0, s>>>(nrows, code8, ddelta, dval, ndict, S, lds, nc, R, ldr);
-  else if (W == 16) k_spmm_ell<16, TR><<<g, kT, 0, s>>>(nrows, code8, ddelta, dval, ndict, S, lds, nc, R, ldr);
-  else return (int)hipErrorInvalidValue;
-  return (int)hipGetLastError();
+  const bool known = pick<4, 8, 16>(W, [&](auto w) {
+    k_spmm_ell<decltype(w)::value, TR><<<g, kT, 0, s>>>(nrows, code8, ddelta, dval, ndict, S, lds, nc, R, ldr);
+  });
+  return known ? (int)hipGetLastError() : (int)hipErrorInvalidValue;
 }
 
 extern "C" int msk_spmm_ell(int32_t nrows, int W, const uint8_t* code8, const int32_t* ddelta, const double* dval,
@@ -2969,12 +2922,13 @@ extern "C" int msk_spmv_mdot(int32_t nrows, const int32_t* rowptr, const int32_t
   if (lds_cap <= 0 || nv < 1 || nv > MSK_MAX_GROUP) return (int)hipErrorInvalidValue;
   const size_t lds = (size_t)lds_cap * 12;
   const dim3 g((unsigned)nchunks), b(kT);
-#define MSK_SMD(VAR_, GF_) \
-  k_spmv_mdot<VAR_, GF_><<<g, b, lds, s>>>(nrows, rowptr, col, val, x, sdev, y, lds_cap, *V, nv, partial, nchunks, stop)
-  const bool g2 = (msk_tuning_flags & MSK_TUNE_SPMV_MDOT_G2) != 0;
-  if (vec_var()) { if (g2) MSK_SMD(1, 2); else MSK_SMD(1, 4); }
-  else { if (g2) MSK_SMD(0, 2); else MSK_SMD(0, 4); }
-#undef MSK_SMD
+  const int gf = (msk_tuning_flags & MSK_TUNE_SPMV_MDOT_G2) ? 2 : 4;  // basis vectors per load group
+  pick<1, 0>(vec_var(), [&](auto var) {
+    pick<4, 2>(gf, [&](auto gfc) {
+      k_spmv_mdot<decltype(var)::value, decltype(gfc)::value><<<g, b, lds, s>>>(nrows, rowptr, col, val, x, sdev, y, lds_cap,
+                                                                              *V, nv, partial, nchunks, stop);
+    });
+  });
   return (int)hipGetLastError();
 }
 
@@ -3000,10 +2954,7 @@ extern "C" int msk_box_spmv_mdot_rv(int32_t nx, int64_t P, int64_t n, int d2, co
   const bool nty = !(msk_tuning_flags & MSK_TUNE_ELL_TEMPORAL_Y);
   if (!d2 && P % kChunk == 0 && n % P == 0 && (nx & 1) == 0 && (rv || !(msk_tuning_flags & MSK_TUNE_BOX_MDOT_FLAT))) {
     // whole chunks per plane: march zt planes per workgroup (MSPLIT_BOXMDOT_ZT overrides the depth, A/B)
-    static const int zenv = [] {
-      const char* e = getenv("MSPLIT_BOXMDOT_ZT");
-      return e ? atoi(e) : 0;
-    }();
+    static const int zenv = env_int("MSPLIT_BOXMDOT_ZT", 0);
     const int32_t nz = (int32_t)(n / P);
     // four planes per workgroup: half the workgroup prologues (the dependent loads of the plane below the first: x,
     // and for the STENCIL storage its z+1 leg) -- STENCIL step +1.9 %, SMSM block +0.3 %, 256^3 GMRES +0.1 % against
@@ -3013,78 +2964,63 @@ extern "C" int msk_box_spmv_mdot_rv(int32_t nx, int64_t P, int64_t n, int d2, co
     if (grid > INT32_MAX) return (int)hipErrorInvalidValue;
     // XCD-contiguous eighths from 32 tiles per plane (SMSM's 512^2 planes: +1.9 % over plane order, same box);
     // smaller planes in plane order (256^2: +1.4 % over the eighths; profiles/r03/boxmdot/xcd/)
-    static const int rev = [] {
-      const char* e = getenv("MSPLIT_BOXMDOT_REV");
-      return e && atoi(e) ? 2 : 0;
-    }();
+    static const int rev = env_int("MSPLIT_BOXMDOT_REV", 0) ? 2 : 0;
     // MSPLIT_BOXMDOT_ALT=1: odd plane groups march down (k_box_spmv_mdot_march, xcd & 4), so the boundary planes
     // two groups both read are read at the same moment, the second time from the L2.  Measured (round 6,
     // profiles/r06/march_alt/): PMC 1.048 -> 1.019 of the algorithmic bytes for the symmetric STENCIL step and
     // 1.035 -> 1.011 for the DV step, but no faster (STENCIL -2.9 %, DV -0.1 %): those re-reads were MALL hits, the
     // kernels are bound by their streaming rate.  Off by default; read per call (the tests hold both orders to each
-    // other and to the oracle).
+    // other and to the oracle).  Its test is the first character, not env_int's number.
     const char* alte = getenv("MSPLIT_BOXMDOT_ALT");
     const int alt = alte && alte[0] == '1' ? 4 : 0;
     const int xcd =
         ((P / kChunk) % 8 == 0 && P / kChunk >= 32 && !(msk_tuning_flags & MSK_TUNE_BOX_MDOT_NOXCD)) | rev | alt;
     // GMRES's basis ends with x (VV(it)): its dot from the march registers (MSPLIT_BOXMDOT_SELF=0: streamed, A/B)
-    static const int self_env = [] {
-      const char* e = getenv("MSPLIT_BOXMDOT_SELF");
-      return e ? atoi(e) : 1;
-    }();
+    static const int self_env = env_int("MSPLIT_BOXMDOT_SELF", 1);
     const double* last = V->base ? V->base + (int64_t)(nv - 1) * V->stride : V->p[nv - 1];
     const int self = self_env != 0 && last == x;
     if (self_out) *self_out = self;
     static const int rvp = [] {  // MSPLIT_RV_PREFETCH: row pairs whose values go before the barriers (8, 4 or 2)
-      const char* e = getenv("MSPLIT_RV_PREFETCH");
-      const int v = e ? atoi(e) : kIters;
+      const int v = env_int("MSPLIT_RV_PREFETCH", kIters);
       return v == 4 || v == 2 ? v : kIters;
     }();
-#define MSK_BSMM_P(VAR_, NT_, RV_, P_)                                                                          \
-  k_box_spmv_mdot_march<VAR_, NT_, RV_, P_><<<dim3((unsigned)grid), b, lds, s>>>(nx, P, nz, zt, xcd, mask, dval, rv, \
-                                                                                 rvs, x, sdev, y, *V, nv, self,     \
-                                                                                 partial, nchunks, stop)
-#define MSK_BSMM(VAR_, NT_, RV_)                                                                              \
-  do {                                                                                                        \
-    if (RV_ == 1 && rvp == 4) MSK_BSMM_P(VAR_, NT_, RV_, 4);                                                  \
-    else if (RV_ == 1 && rvp == 2) MSK_BSMM_P(VAR_, NT_, RV_, 2);                                             \
-    else MSK_BSMM_P(VAR_, NT_, RV_, kIters);                                                                  \
-  } while (0)
     // the symmetric storage: two threads per DBR lane where the windows fit (nx <= 512; MSPLIT_RV_SYM2=0: one, A/B)
-    const char* s2e = getenv("MSPLIT_RV_SYM2");  // read per call: the tests hold the two forms to each other
+    // read per call: the tests hold the two forms to each other; its test is the first character, not env_int's number
+    const char* s2e = getenv("MSPLIT_RV_SYM2");
     const bool sym2 = !(s2e && s2e[0] == '0') && nx <= 512;
-#define MSK_SYM2(VAR_, NT_)                                                                               \
-  k_box_spmv_mdot_march_sym2<VAR_, NT_><<<dim3((unsigned)grid), dim3(2 * kT), lds, s>>>(                   \
-      nx, P, nz, zt, xcd, mask, rv, x, sdev, y, *V, nv, self, partial, nchunks, stop)
-    if (rv && rvs < 0 && sym2) {
-      if (vec_var()) { if (nty) MSK_SYM2(1, true); else MSK_SYM2(1, false); }
-      else { if (nty) MSK_SYM2(0, true); else MSK_SYM2(0, false); }
-    } else if (rv && rvs < 0) {  // the symmetric storage
-      if (vec_var()) { if (nty) MSK_BSMM(1, true, 2); else MSK_BSMM(1, false, 2); }
-      else { if (nty) MSK_BSMM(0, true, 2); else MSK_BSMM(0, false, 2); }
-    } else if (rv) {
-      if (vec_var()) { if (nty) MSK_BSMM(1, true, 1); else MSK_BSMM(1, false, 1); }
-      else { if (nty) MSK_BSMM(0, true, 1); else MSK_BSMM(0, false, 1); }
-    } else {
-      if (vec_var()) { if (nty) MSK_BSMM(1, true, 0); else MSK_BSMM(1, false, 0); }
-      else { if (nty) MSK_BSMM(0, true, 0); else MSK_BSMM(0, false, 0); }
-    }
-#undef MSK_SYM2
-#undef MSK_BSMM
-#undef MSK_BSMM_P
+    const int form = rv_form(rv, rvs);
+    pick<1, 0>(vec_var(), [&](auto var) {
+      pick<true, false>(nty, [&](auto nt) {
+        constexpr int VAR = decltype(var)::value;
+        constexpr bool NT = decltype(nt)::value;
+        if (form == 2 && sym2) {
+          k_box_spmv_mdot_march_sym2<VAR, NT><<<dim3((unsigned)grid), dim3(2 * kT), lds, s>>>(
+              nx, P, nz, zt, xcd, mask, rv, x, sdev, y, *V, nv, self, partial, nchunks, stop);
+          return;
+        }
+        pick<0, 1, 2>(form, [&](auto f) {
+          constexpr int RV = decltype(f)::value;
+          auto go = [&](auto p) {
+            k_box_spmv_mdot_march<VAR, NT, RV, decltype(p)::value><<<dim3((unsigned)grid), b, lds, s>>>(
+                nx, P, nz, zt, xcd, mask, dval, rv, rvs, x, sdev, y, *V, nv, self, partial, nchunks, stop);
+          };
+          // only the rows' own values (RV == 1) take the shorter prefetches.  The test is a run-time one, as it always
+          // was, so the library goes on holding the P = 4 and P = 2 kernels of the other two forms, which nothing
+          // launches (profiles/launch_dispatch/README.md); retiring them is a change of its own.
+          pick<kIters, 4, 2>(RV == 1 ? rvp : kIters, go);
+        });
+      });
+    });
     return (int)hipGetLastError();
   }
-#define MSK_BSM(D, VAR_, NT_) \
-  k_box_spmv_mdot<D, VAR_, NT_><<<g, b, lds, s>>>(nx, P, n, mask, dval, x, sdev, y, *V, nv, partial, nchunks, stop)
-#define MSK_BSM2(D)                                              \
-  do {                                                           \
-    if (vec_var()) { if (nty) MSK_BSM(D, 1, true); else MSK_BSM(D, 1, false); } \
-    else { if (nty) MSK_BSM(D, 0, true); else MSK_BSM(D, 0, false); }           \
-  } while (0)
-  if (d2) MSK_BSM2(true);
-  else MSK_BSM2(false);
-#undef MSK_BSM2
-#undef MSK_BSM
+  pick<true, false>(d2 != 0, [&](auto d) {
+    pick<1, 0>(vec_var(), [&](auto var) {
+      pick<true, false>(nty, [&](auto nt) {
+        k_box_spmv_mdot<decltype(d)::value, decltype(var)::value, decltype(nt)::value><<<g, b, lds, s>>>(
+            nx, P, n, mask, dval, x, sdev, y, *V, nv, partial, nchunks, stop);
+      });
+    });
+  });
   return (int)hipGetLastError();
 }
 
@@ -3113,51 +3049,28 @@ extern "C" int msk_box_maxpy_march(int32_t nx, int64_t P, int64_t n, int d2, con
     const int64_t nch = (n + kChunk - 1) / kChunk;
     if (nch > INT32_MAX) return (int)hipErrorInvalidValue;
     const size_t ldsu = (size_t)(kChunk + 2 * nx) * sizeof(double);
-#define MSK_BMU(D_, VAR_, NT_)                                                                                      \
-  k_box_maxpy<D_, VAR_, NT_><<<dim3((unsigned)nch), dim3(kT), ldsu, s>>>(nx, P, n, mask, dval, x, sdev, wout, *V, nv, \
-                                                                        adev, partial, stop)
-#define MSK_BMU2(D_)                                                                          \
-  do {                                                                                        \
-    if (vec_var()) { if (nt) MSK_BMU(D_, 1, true); else MSK_BMU(D_, 1, false); }              \
-    else { if (nt) MSK_BMU(D_, 0, true); else MSK_BMU(D_, 0, false); }                        \
-  } while (0)
-    if (d2) MSK_BMU2(true);
-    else MSK_BMU2(false);
-#undef MSK_BMU2
-#undef MSK_BMU
+    pick<true, false>(d2 != 0, [&](auto d) {
+      pick<1, 0>(vec_var(), [&](auto var) {
+        pick<true, false>(nt, [&](auto ntc) {
+          k_box_maxpy<decltype(d)::value, decltype(var)::value, decltype(ntc)::value>
+              <<<dim3((unsigned)nch), dim3(kT), ldsu, s>>>(nx, P, n, mask, dval, x, sdev, wout, *V, nv, adev, partial, stop);
+        });
+      });
+    });
     return (int)hipGetLastError();
   }
-  static const int zenv = [] {
-    const char* e = getenv("MSPLIT_MAXPY_ZT");
-    return e ? atoi(e) : 0;
-  }();
-  static const int rev_env = [] {
-    const char* e = getenv("MSPLIT_MAXPY_REV");
-    return e ? (atoi(e) ? 1 : 0) : -1;
-  }();
+  static const int zenv = env_int("MSPLIT_MAXPY_ZT", 0);
   const int32_t nz = (int32_t)(n / P);
   // one plane per workgroup (x(z-+1) loaded per plane, twice the workgroups of the fused kernel's 2-plane march):
   // 256^3 GMRES step 2.261 -> 2.336e10 over 2 planes, MAXPY 392 -> 368 us (profiles/r03/wfree/ab/)
   const int32_t zt = zenv > 0 ? zenv : 1;
   const int64_t grid = (P / kChunk) * ((nz + zt - 1) / zt);
   if (grid > INT32_MAX) return (int)hipErrorInvalidValue;
-  const int rev = (rev_env < 0 ? n > ((int64_t)1 << 25) : rev_env) ? 2 : 0;
+  const int rev = maxpy_rev(n) ? 2 : 0;  // msk_maxpy_chunk's order
   const int xcd = ((P / kChunk) % 8 == 0 && P / kChunk >= 32 && !(msk_tuning_flags & MSK_TUNE_BOX_MDOT_NOXCD)) | rev;
   const size_t lds = (size_t)(kChunk + 2 * nx) * sizeof(double);
-  const bool nty = nt;
   // MSPLIT_MAXPY_MARCH_U2=1: the group loop unrolled by two (A/B)
-  static const int u2 = [] {
-    const char* e = getenv("MSPLIT_MAXPY_MARCH_U2");
-    return e ? atoi(e) : 0;
-  }();
-#define MSK_BMM(VAR_, NT_, PF_)                                                                              \
-  k_box_maxpy_march<VAR_, NT_, PF_><<<dim3((unsigned)grid), dim3(kT), lds, s>>>(                                \
-      nx, P, nz, zt, xcd, mask, dval, x, sdev, wout, *V, nv, adev, partial, stop)
-#define MSK_BMM2(PF_)                                                              \
-  do {                                                                             \
-    if (vec_var()) { if (nty) MSK_BMM(1, true, PF_); else MSK_BMM(1, false, PF_); } \
-    else { if (nty) MSK_BMM(0, true, PF_); else MSK_BMM(0, false, PF_); }           \
-  } while (0)
+  static const int u2 = env_int("MSPLIT_MAXPY_MARCH_U2", 0);
   // the one-plane form where one plane per workgroup runs (MSPLIT_MAXPY_ZT > 1 keeps the marched form)
   // By nv (mode 1): the one-plane form runs one wave per SIMD (its registers do not fit two), so nothing covers a
   // workgroup's prologue but its own prefetch, and a launch costs about 28 us more at nv = 1 (256^3: 93 against
@@ -3168,12 +3081,17 @@ extern "C" int msk_box_maxpy_march(int32_t nx, int64_t P, int64_t n, int d2, con
   constexpr int kOnePlaneFromNv = 16;
   const int mode = zt == 1 ? msk_maxpy_prefetch : 0;
   const int pf = mode == 1 ? (nv >= kOnePlaneFromNv ? 2 : 0) : mode;
-  if (pf == 3) MSK_BMM2(2);
-  else if (pf == 2) MSK_BMM2(1);
-  else if (u2 && vec_var() && nty) MSK_BMM(33, true, 0);
-  else MSK_BMM2(0);
-#undef MSK_BMM2
-#undef MSK_BMM
+  const int form = pf == 3 ? 2 : pf == 2 ? 1 : 0;  // the kernel's PF: 0 marched, 1 one plane, 2 its 8-vector burst
+  auto go = [&](auto var, auto ntc, auto f) {
+    k_box_maxpy_march<decltype(var)::value, decltype(ntc)::value, decltype(f)::value>
+        <<<dim3((unsigned)grid), dim3(kT), lds, s>>>(nx, P, nz, zt, xcd, mask, dval, x, sdev, wout, *V, nv, adev, partial, stop);
+  };
+  if (form == 0 && u2 && vec_var() && nt)  // the unrolled loop exists for the marched form with both policies on only
+    go(std::integral_constant<int, 33>{}, std::true_type{}, std::integral_constant<int, 0>{});
+  else
+    pick<0, 1, 2>(form, [&](auto f) {
+      pick<1, 0>(vec_var(), [&](auto var) { pick<true, false>(nt, [&](auto ntc) { go(var, ntc, f); }); });
+    });
   return (int)hipGetLastError();
 }
 
@@ -3203,8 +3121,9 @@ extern "C" int msk_spmv_rows(int32_t nlisted, const int32_t* row_ids, const int3
                              hipStream_t s) {
   if (nlisted <= 0) return 0;
   const unsigned g = (unsigned)((nlisted + kT - 1) / kT);
-  if (resid) k_spmv_rows<true><<<dim3(g), dim3(kT), 0, s>>>(nlisted, row_ids, rowptr, col, val, x, b, y);
-  else k_spmv_rows<false><<<dim3(g), dim3(kT), 0, s>>>(nlisted, row_ids, rowptr, col, val, x, b, y);
+  pick<true, false>(resid != 0, [&](auto r) {
+    k_spmv_rows<decltype(r)::value><<<dim3(g), dim3(kT), 0, s>>>(nlisted, row_ids, rowptr, col, val, x, b, y);
+  });
   return (int)hipGetLastError();
 }
 
@@ -3225,11 +3144,12 @@ extern "C" int msk_stencil_spmv(int dim, int32_t nx, int32_t ny, int32_t nz, int
                   (!b || ((uintptr_t)b & 15) == 0) && (!vout || ((uintptr_t)vout & 15) == 0) && (!lo || P % 2 == 0);
   const int per = v2 ? 2 * kT : kT;
   const dim3 g((unsigned)((nx + per - 1) / per), (unsigned)ny, (unsigned)(dim == 3 ? nz : 1));
-#define MSK_ST(M, V) k_stencil_spmv<M, V><<<g, dim3(kT), 0, s>>>(dim, nx, ny, nz, lo, hi, *cf, x, b, y, sdev, vout, stop)
-  if (mode == MSK_SPMV_RESID) { if (v2) MSK_ST(MSK_SPMV_RESID, true); else MSK_ST(MSK_SPMV_RESID, false); }
-  else if (mode == MSK_SPMV_SCALED) { if (v2) MSK_ST(MSK_SPMV_SCALED, true); else MSK_ST(MSK_SPMV_SCALED, false); }
-  else { if (v2) MSK_ST(MSK_SPMV_MULT, true); else MSK_ST(MSK_SPMV_MULT, false); }
-#undef MSK_ST
+  pick_mode(mode, [&](auto m) {
+    pick<true, false>(v2, [&](auto v) {
+      k_stencil_spmv<decltype(m)::value, decltype(v)::value><<<g, dim3(kT), 0, s>>>(dim, nx, ny, nz, lo, hi, *cf, x, b, y, sdev,
+                                                                                  vout, stop);
+    });
+  });
   return (int)hipGetLastError();
 }
 
@@ -3237,15 +3157,8 @@ extern "C" int msk_blas1(int op, double* y, const double* x, const double* z, do
                          hipStream_t s) {
   if (n <= 0) return 0;
   const int g = grid_for(n, 4096);
-  switch (op) {
-    case MSK_SET: k_blas1<MSK_SET><<<dim3(g), dim3(kT), 0, s>>>(y, x, z, alpha, n); break;
-    case MSK_COPY: k_blas1<MSK_COPY><<<dim3(g), dim3(kT), 0, s>>>(y, x, z, alpha, n); break;
-    case MSK_SCALE: k_blas1<MSK_SCALE><<<dim3(g), dim3(kT), 0, s>>>(y, x, z, alpha, n); break;
-    case MSK_AXPY: k_blas1<MSK_AXPY><<<dim3(g), dim3(kT), 0, s>>>(y, x, z, alpha, n); break;
-    case MSK_AYPX: k_blas1<MSK_AYPX><<<dim3(g), dim3(kT), 0, s>>>(y, x, z, alpha, n); break;
-    case MSK_WAXPY_P1: k_blas1<MSK_WAXPY_P1><<<dim3(g), dim3(kT), 0, s>>>(y, x, z, alpha, n); break;
-    case MSK_WAXPY_M1: k_blas1<MSK_WAXPY_M1><<<dim3(g), dim3(kT), 0, s>>>(y, x, z, alpha, n); break;
-    default: k_blas1<MSK_WAXPY><<<dim3(g), dim3(kT), 0, s>>>(y, x, z, alpha, n); break;
-  }
+  auto go = [&](auto o) { k_blas1<(int)decltype(o)::value><<<dim3(g), dim3(kT), 0, s>>>(y, x, z, alpha, n); };
+  if (!pick<MSK_SET, MSK_COPY, MSK_SCALE, MSK_AXPY, MSK_AYPX, MSK_WAXPY_P1, MSK_WAXPY_M1>(op, go))
+    go(std::integral_constant<int, MSK_WAXPY>{});  // every other value
   return (int)hipGetLastError();
 }
