@@ -106,7 +106,7 @@ static int opt_bool(const msd_options *o, const char *prefix, const char *key, i
 /* ------------------------------------------------------------------- layout */
 /* utils.py block_layout: z-slabs (3D) or whole mesh lines (2D). */
 int msd_layout_make(int dim, int32_t nx, int32_t ny, int32_t nz, int nb, int b, const double *peclet,
-                    msd_layout *L) {
+                    const uint64_t *kappa_seed, msd_layout *L) {
   memset(L, 0, sizeof(*L));
   if (nb < 1 || nb > MSD_MAX_BLOCKS || b < 0 || b >= nb) return MSP_ERR_ARG_OUTOFRANGE;
   L->dim = dim;
@@ -145,14 +145,58 @@ int msd_layout_make(int dim, int32_t nx, int32_t ny, int32_t nz, int nb, int b, 
     L->box[3] = 1;
   }
   for (int d = 0; d < 3; ++d) L->peclet[d] = peclet ? peclet[d] : 0.0;
+  L->has_kappa = kappa_seed != NULL;
+  L->kappa_seed = kappa_seed ? *kappa_seed : 0;
   return MSP_SUCCESS;
 }
+
+static uint64_t splitmix64(uint64_t x) {
+  uint64_t z = x + 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+double msd_cell_coefficient(uint64_t seed, int64_t cell) {
+  const double m = (double)(splitmix64((uint64_t)cell + seed) % 1000u) * 0.001;
+  return 1.0 + m;
+}
+
+double msd_face_weight(double ka, double kb) { return ((2.0 * ka) * kb) / (ka + kb); }
 
 /* coupling values: the slow-direction lower / upper coefficients (utils.py convdiff_coefs) */
 static void slow_coefs(const msd_layout *L, double *lo, double *hi) {
   const double p = L->dim == 3 ? L->peclet[2] : L->peclet[1];
   *lo = -1.0 - 2.0 * (p > 0.0 ? p : 0.0);
   *hi = -1.0 + 2.0 * (p < 0.0 ? p : 0.0);
+}
+
+double msd_layout_coupling(const msd_layout *L, int64_t l, int up) {
+  if (!L->has_kappa) {
+    double lo, hi;
+    slow_coefs(L, &lo, &hi);
+    return up ? hi : lo;
+  }
+  const int64_t a = L->r0 + l, b = up ? a + L->plane : a - L->plane; /* global cells: the row's and its neighbour's */
+  return -msd_face_weight(msd_cell_coefficient(L->kappa_seed, a), msd_cell_coefficient(L->kappa_seed, b));
+}
+
+/* A block's rows assembled on the device, the columns of the plane below / above kept with lo / hi
+ * (multisplitting.py box_operator): with a kappa the diffusion operator, its coefficients filled on the device for
+ * [ghost plane below | the block | ghost plane above] -- the neighbour blocks' boundary planes, whose kappa the face
+ * weights read whether or not their columns are kept -- else Poisson / convection-diffusion. */
+static int box_operator(msp_ctx *ctx, const msd_layout *L, int lo, int hi, msp_mat **A) {
+  if (!L->has_kappa)
+    return msp_mat_create_box_convdiff(ctx, L->box[0], L->box[1], L->box[2], L->box[3], lo, hi, L->peclet, A);
+  const int64_t glo = L->has_lo ? L->plane : 0, ghi = L->has_hi ? L->plane : 0;
+  msp_vec *kap = NULL;
+  int rc = msp_vec_create(ctx, glo + (L->r1 - L->r0) + ghi, &kap);
+  if (!rc) rc = msp_vec_set_cell_coefficients(kap, L->r0 - glo, L->kappa_seed);
+  if (!rc)
+    rc = msp_mat_create_box_diffusion(ctx, L->box[0], L->box[1], L->box[2], L->box[3], L->has_lo, L->has_hi, lo, hi,
+                                      kap, A);
+  msp_vec_destroy(&kap);
+  return rc;
 }
 
 /* -------------------------------------------------------------------- block */
@@ -266,21 +310,19 @@ static int release_csr_if_dv(msp_mat *M) {
 
 static int block_init(msp_ctx *ctx, const msd_problem *p, const msd_options *o, int b, msd_block *B) {
   memset(B, 0, sizeof(*B));
-  CK(msd_layout_make(p->dim, p->nx, p->ny, p->nz, p->nb, b, p->peclet, &B->L));
+  CK(msd_layout_make(p->dim, p->nx, p->ny, p->nz, p->nb, b, p->peclet, p->has_kappa ? &p->kappa_seed : NULL, &B->L));
   msd_layout *L = &B->L;
   B->n = L->r1 - L->r0;
   B->lo = L->has_lo ? L->plane : 0;
   B->hi = L->has_hi ? L->plane : 0;
   if (p->matfree) CK(msp_mat_create_box_matfree(ctx, L->box[0], L->box[1], L->box[2], L->box[3], 0, 0, L->peclet, &B->A));
-  else CK(msp_mat_create_box_convdiff(ctx, L->box[0], L->box[1], L->box[2], L->box[3], 0, 0, L->peclet, &B->A));
+  else CK(box_operator(ctx, L, 0, 0, &B->A));
   /* initializeKSP's prefix, inner{b+1}_; Jacobi reads the operator's diagonal from its CSR, which then stays */
   char prefix[32];
   snprintf(prefix, sizeof(prefix), "inner%d_", b + 1);
   if (strcasecmp(msd_opt_str(o, prefix, "pc_type", "none"), "jacobi")) CK(release_csr_if_dv(B->A));
   /* coupling rows in halo numbering: row l < plane reads halo[l] (below), row l >= n-plane reads
    * halo[lo + l - (n-plane)] (above); ascending halo index = ascending global column */
-  double clo, chi;
-  slow_coefs(L, &clo, &chi);
   int32_t *rid = (int32_t *)malloc(sizeof(int32_t) * (size_t)(2 * L->plane + 1));
   int32_t *rp = (int32_t *)malloc(sizeof(int32_t) * (size_t)(2 * L->plane + 2));
   int32_t *cl = (int32_t *)malloc(sizeof(int32_t) * (size_t)(2 * L->plane + 1));
@@ -291,8 +333,8 @@ static int block_init(msp_ctx *ctx, const msd_problem *p, const msd_options *o, 
   for (int64_t l = 0; l < B->n; ++l) {
     const int dn = L->has_lo && l < L->plane, up = L->has_hi && l >= B->n - L->plane;
     if (!dn && !up) continue;
-    if (dn) { cl[ne] = (int32_t)l; vl[ne++] = clo; }
-    if (up) { cl[ne] = (int32_t)(B->lo + l - (B->n - L->plane)); vl[ne++] = chi; }
+    if (dn) { cl[ne] = (int32_t)l; vl[ne++] = msd_layout_coupling(L, l, 0); }
+    if (up) { cl[ne] = (int32_t)(B->lo + l - (B->n - L->plane)); vl[ne++] = msd_layout_coupling(L, l, 1); }
     rid[nl++] = (int32_t)l;
     rp[nl] = ne;
   }
@@ -312,8 +354,7 @@ static int block_init(msp_ctx *ctx, const msd_problem *p, const msd_options *o, 
   CK(msp_vec_create(ctx, B->n, &B->d));
   CK(msp_vec_create(ctx, B->lo + B->n + B->hi, &B->xe));
   /* computeTheRightHandSideWithInitialGuess (utils.c:623-650): b_i = A_block 1 */
-  CK(msp_mat_create_box_convdiff(ctx, L->box[0], L->box[1], L->box[2], L->box[3], B->lo > 0, B->hi > 0, L->peclet,
-                                 &B->A_ext));
+  CK(box_operator(ctx, L, B->lo > 0, B->hi > 0, &B->A_ext));
   CK(release_csr_if_dv(B->A_ext));
   CK(msp_vec_set(B->xe, 1.0));
   CK(msp_mat_mult(B->A_ext, B->xe, B->b));
@@ -804,7 +845,7 @@ static int amam_setup_block(msp_ctx *ctx, const msd_problem *p, const msd_option
       continue;
     }
     msd_layout Lj;
-    CK(msd_layout_make(p->dim, p->nx, p->ny, p->nz, p->nb, j, p->peclet, &Lj));
+    CK(msd_layout_make(p->dim, p->nx, p->ny, p->nz, p->nb, j, p->peclet, p->has_kappa ? &p->kappa_seed : NULL, &Lj));
     const int64_t nj = Lj.r1 - Lj.r0, loj = Lj.has_lo ? Lj.plane : 0, hij = Lj.has_hi ? Lj.plane : 0;
     /* the replicated rows of R take R's precision (the Gram parts and Gsum above stay double) */
     CK(msp_dense_create_prec(ctx, nj, p->s, p->r_f32 ? MSP_DENSE_F32 : MSP_DENSE_F64, &B->Rrep[j]));
@@ -812,8 +853,7 @@ static int amam_setup_block(msp_ctx *ctx, const msd_problem *p, const msd_option
     /* b_j = A_block_j 1 (utils.c:623-650) */
     msp_mat *Aj;
     msp_vec *ones, *bj;
-    CK(msp_mat_create_box_convdiff(ctx, Lj.box[0], Lj.box[1], Lj.box[2], Lj.box[3], loj > 0, hij > 0, Lj.peclet,
-                                   &Aj));
+    CK(box_operator(ctx, &Lj, loj > 0, hij > 0, &Aj));
     CK(msp_vec_create(ctx, loj + nj + hij, &ones));
     CK(msp_vec_set(ones, 1.0));
     CK(msp_vec_create(ctx, nj, &bj));
@@ -895,7 +935,7 @@ int msd_amam_global_solve(msp_ctx *ctx, const msd_problem *p, const msd_options 
   int64_t cap = p->rtr ? (int64_t)p->s * (p->s + 1) : 0;
   for (int j = 0; j < p->nb && !p->rtr; ++j) {
     msd_layout Lj;
-    CK(msd_layout_make(p->dim, p->nx, p->ny, p->nz, p->nb, j, p->peclet, &Lj));
+    CK(msd_layout_make(p->dim, p->nx, p->ny, p->nz, p->nb, j, p->peclet, p->has_kappa ? &p->kappa_seed : NULL, &Lj));
     int64_t c = (Lj.r1 - Lj.r0) * (int64_t)p->s;
     if (p->r_f32) c = (c + 1) / 2; /* cap counts doubles: two floats of a single-precision R fill one */
     if (c > cap) cap = c;

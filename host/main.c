@@ -2,7 +2,7 @@
  * main.c -- the reference's multisplitting executables as a C host:
  *
  *   msplit_driver <program> -m M -n N [-s S] [-rtol R] [-atol A] [-dim 3 -p P]
- *                 [-peclet px,py,pz] [-nb B] [-json] [-inner{b}_ksp_* ...] [-outer{b}_ksp_* ...]
+ *                 [-peclet px,py,pz | -kappa_seed S] [-nb B] [-json] [-inner{b}_ksp_* ...] [-outer{b}_ksp_* ...]
  *
  * <program>: synchronous-multisplitting,
  *            synchronous-multisplitting-synchronous-minimization-global,
@@ -46,7 +46,7 @@ static int usage(void) {
   fprintf(stderr, "usage: msplit_driver <synchronous-multisplitting | "
                   "synchronous-multisplitting-synchronous-minimization-global | asynchronous-multisplitting | "
                   "asynchronous-multisplitting-asynchronous-minimization-global> "
-                  "-m M -n N [-s S] [-rtol R] [-dim 3 -p P] [-peclet px,py,pz] [-nb B] [-msplit_reduction dbr|seq] [-msplit_minimization lsqr|rtr] "
+                  "-m M -n N [-s S] [-rtol R] [-dim 3 -p P] [-peclet px,py,pz | -kappa_seed S] [-nb B] [-msplit_reduction dbr|seq] [-msplit_minimization lsqr|rtr] "
                   "[-msplit_minimization_precision double|single] [-innerK_msplit_basis_precision double|single|block16] "
                   "[-innerK_pc_type none|jacobi] [-innerK_msplit_operator_precision double|single] "
                   "[-innerK_ksp_gmres_cgs_refinement_type refine_never|refine_ifneeded|refine_always] [-json] ...\n");
@@ -93,6 +93,21 @@ int main(int argc, char **argv) {
   p.r_f32 = !strcasecmp(mprec, "single");
   const char *pe = msd_opt_str(o, NULL, "peclet", NULL);
   if (pe && sscanf(pe, "%lf,%lf,%lf", &p.peclet[0], &p.peclet[1], &p.peclet[2]) != 3) return usage();
+  /* -kappa_seed S: the variable-coefficient diffusion operator with the hashed field of seed S, one operator at a
+   * time (not with a non-zero -peclet) and assembled (it has no matrix-free form) */
+  const char *ks = msd_opt_str(o, NULL, "kappa_seed", NULL);
+  if (ks) {
+    p.has_kappa = 1;
+    p.kappa_seed = (uint64_t)strtoll(ks, NULL, 10);
+    if (p.peclet[0] != 0.0 || p.peclet[1] != 0.0 || p.peclet[2] != 0.0) {
+      fprintf(stderr, "-kappa_seed with a non-zero -peclet: two operators\n");
+      return usage();
+    }
+    if (p.matfree) {
+      fprintf(stderr, "-kappa_seed with -msplit_operator matfree: the diffusion operator has no matrix-free form\n");
+      return usage();
+    }
+  }
   if (msd_opt_int(o, NULL, "npb", 1) != 1) {
     fprintf(stderr, "-npb must be 1: one GPU (one process) per block\n");
     return 2;

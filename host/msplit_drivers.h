@@ -43,10 +43,20 @@ typedef struct {
   int64_t halo_size;   /* [plane of b-1 | plane of b+1] */
   int32_t box[4];      /* dim, fast, middle, slow extents of A_ii's box stencil */
   double peclet[3];
+  int has_kappa;       /* the diffusion operator -div(kappa grad u) with the hashed field of kappa_seed (-kappa_seed) */
+  uint64_t kappa_seed;
 } msd_layout;
 
+/* kappa_seed: NULL for Poisson / convection-diffusion, else the seed of the diffusion operator's hashed field */
 int msd_layout_make(int dim, int32_t nx, int32_t ny, int32_t nz, int nb, int b, const double *peclet,
-                    msd_layout *L);
+                    const uint64_t *kappa_seed, msd_layout *L);
+/* The hashed field in plain C (utils.py cell_coefficients): kappa(c) = 1.0 + (splitmix64(c + seed) mod 1000) * 0.001,
+ * one multiply, then one add; and the face weight ((2 ka) kb) / (ka + kb) (utils.py diffusion_rows). */
+double msd_cell_coefficient(uint64_t seed, int64_t cell);
+double msd_face_weight(double ka, double kb);
+/* The coupling value of local row l towards the plane below (up = 0) or above (up = 1): the constant slow-direction
+ * coefficient, or with a kappa -w of the face between the row's cell and its neighbour in the other block. */
+double msd_layout_coupling(const msd_layout *L, int64_t l, int up);
 
 /* ---- transport: all blocks local (world == 1) or one block per rank ---- */
 typedef struct {
@@ -79,6 +89,8 @@ typedef struct {
   double rtol, atol, peclet[3];
   int max_outer;
   int matfree;             /* -msplit_operator matfree: A_ii without storage */
+  int has_kappa;           /* -kappa_seed S: the diffusion operator with the hashed field of seed S */
+  uint64_t kappa_seed;
   int async_host;          /* -msplit_async_transport host: shared-memory staging instead of HBM slots */
   int rtr;                 /* -msplit_minimization rtr: AMAM-global through outer_solver's normal equations */
   int r_f32;               /* -msplit_minimization_precision single: R = A S (and the replicated R) stored as float */

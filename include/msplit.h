@@ -168,6 +168,27 @@ int msp_mat_create_box_stencil_ext(msp_ctx *ctx, int dim, int32_t nx, int32_t ny
  * column layout as msp_mat_create_box_stencil_ext. */
 int msp_mat_create_box_convdiff(msp_ctx *ctx, int dim, int32_t nx, int32_t ny, int32_t nz, int32_t lo, int32_t hi,
                                 const double *peclet, msp_mat **A);
+/* The variable-coefficient diffusion operator -div(kappa grad u) on the same boxes (build-defined; the reference
+ * has only Poisson), one coefficient per cell, assembled in HBM from a coefficient vector that is already there.
+ * kappa holds (ghost_lo + ns + ghost_hi) * plane doubles, ns = nz (dim 3) or ny (dim 2), plane = nx*ny or nx:
+ * [ghost plane below | the block's planes | ghost plane above]; ghost_lo / ghost_hi in {0,1} say whether the global
+ * problem has a plane of cells there, whose kappa enters the block's face weights (and so its diagonal) even when
+ * its columns are dropped.  The face between the row's cell a and a neighbour cell b weighs
+ * w = ((2 ka) kb) / (ka + kb); a face with no cell behind it (the box sides in x and y, a slow side without a ghost
+ * plane) the cell's own kappa.  Off-diagonal entries are -w; the diagonal is the sum of the face weights in the order
+ * slow-, y-, x-, x+, y+, slow+ (dim 2: slow-, x-, x+, slow+), left to right.  Every *, + and / rounds on its own (no
+ * libm, no contraction); kappa is not validated: zero, negative, inf and NaN pass through as IEEE arithmetic gives
+ * them.  kappa = 1 everywhere gives the Poisson stencil bit for bit; lo = hi = 0 gives a bitwise symmetric matrix.
+ * lo / hi keep the columns of the ghost plane below / above (lo <= ghost_lo, hi <= ghost_hi): same block / column
+ * layout as msp_mat_create_box_stencil_ext.  kappa is read during the call only; the matrix keeps its CSR arrays
+ * resident (get_csr, get_diagonal, MatMatMult, Jacobi, MSP_OPER_F32 all work).  No dictionary fits per-row values, so
+ * there is no DV storage; a square 3D block (lo = hi = 0) whose shape qualifies (MSP_STORAGE_STENCIL below) also gets
+ * the STENCIL storage, built on the device from the assembled CSR -- what msp_mat_create_csr would build from the
+ * same arrays, without a host copy.  Errors: MSP_ERR_ARG_OUTOFRANGE for dim, a non-positive extent, nz != 1 in 2D, a
+ * flag outside {0,1}, lo > ghost_lo, hi > ghost_hi or more than 2^31-1 entries; MSP_ERR_ARG_SIZ for a kappa of the
+ * wrong length; MSP_ERR_ARG_WRONG for a kappa of another context.  On failure *A is NULL. */
+int msp_mat_create_box_diffusion(msp_ctx *ctx, int dim, int32_t nx, int32_t ny, int32_t nz, int32_t ghost_lo,
+                                 int32_t ghost_hi, int32_t lo, int32_t hi, const msp_vec *kappa, msp_mat **A);
 int msp_mat_destroy(msp_mat **A);
 int msp_mat_get_info(const msp_mat *A, int32_t *nrows, int32_t *ncols, int64_t *nnz);
 /* Storage of an assembled matrix in HBM (the values and the order of every
@@ -261,6 +282,11 @@ int msp_vec_get_values(const msp_vec *v, int64_t off, int64_t n, double *host);
 int msp_vec_copy_range(const msp_vec *src, int64_t src_off, msp_vec *dst, int64_t dst_off, int64_t n);
 int msp_vec_set(msp_vec *v, double alpha);                                  /* VecSet */
 int msp_vec_copy(const msp_vec *x, msp_vec *y);                             /* VecCopy */
+/* The hashed per-cell coefficient field of the diffusion operator's tests and benchmarks (build-defined, like the
+ * convection-diffusion operator): kappa[i] = 1.0 + (double)(splitmix64(first_cell + i + seed) mod 1000) * 0.001 for
+ * the global cell index first_cell + i, written on the device (64-bit integer arithmetic, one multiply, then one
+ * add: the bits of utils.cell_coefficients on every machine).  Fills the whole vector. */
+int msp_vec_set_cell_coefficients(msp_vec *kappa, int64_t first_cell, uint64_t seed);
 int msp_vec_scale(msp_vec *x, double alpha);                                /* VecScale */
 int msp_vec_axpy(msp_vec *y, double alpha, const msp_vec *x);               /* VecAXPY */
 int msp_vec_aypx(msp_vec *y, double beta, const msp_vec *x);                /* VecAYPX */

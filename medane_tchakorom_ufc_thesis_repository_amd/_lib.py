@@ -84,6 +84,7 @@ _SIGS = {
     "msp_vec_get_values": [_vp, C.c_int64, C.c_int64, _dp],
     "msp_vec_copy_range": [_vp, C.c_int64, _vp, C.c_int64, C.c_int64],
     "msp_vec_set": [_vp, C.c_double],
+    "msp_vec_set_cell_coefficients": [_vp, C.c_int64, C.c_uint64],
     "msp_vec_copy": [_vp, _vp],
     "msp_vec_scale": [_vp, C.c_double],
     "msp_vec_axpy": [_vp, C.c_double, _vp],
@@ -124,6 +125,8 @@ _SIGS = {
                                    _P(_vp)],
     "msp_mat_create_box_convdiff": [_vp, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp,
                                     _P(_vp)],
+    "msp_mat_create_box_diffusion": [_vp, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                     C.c_int32, _vp, _P(_vp)],
     "msp_mat_set_storage": [_vp, C.c_int],
     "msp_mat_get_storage": [_vp, _i32p, _i32p],
     "msp_mat_release_csr": [_vp],

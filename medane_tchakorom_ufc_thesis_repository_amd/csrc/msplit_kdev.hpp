@@ -130,6 +130,28 @@ __device__ __forceinline__ void ell_rows(const EllOp& op, const int32_t* sdel, c
   }
 }
 
+// ---------------------------------------------- box assembly (msplit_kernels.hip, msplit_k_diffusion.hip)
+// Row pointers of a box stencil with Dirichlet boundaries in closed form (entries
+// before row l = deg*l minus the missing neighbours of rows < l).
+__device__ __forceinline__ int64_t box_rowptr(int dim, int64_t l, int64_t nx, int64_t ny, int64_t nz) {
+  const int64_t cx0 = (l + nx - 1) / nx, cxN = l / nx;  // rows < l with i == 0 / i == nx-1
+  const int64_t P = nx * ny;
+  int64_t missing = cx0 + cxN;
+  if (dim == 3) {
+    const int64_t q = l / P, rem = l % P;
+    const int64_t cy0 = q * nx + min(rem, nx);
+    const int64_t cyN = q * nx + max((int64_t)0, rem - (ny - 1) * nx);
+    const int64_t cz0 = min(l, P);
+    const int64_t czN = max((int64_t)0, l - (nz - 1) * P);
+    missing += cy0 + cyN + cz0 + czN;
+    return 7 * l - missing;
+  }
+  const int64_t cy0 = min(l, nx);
+  const int64_t cyN = max((int64_t)0, l - (ny - 1) * nx);
+  missing += cy0 + cyN;
+  return 5 * l - missing;
+}
+
 __device__ __forceinline__ double wave_butterfly(double v) {
   // v[l] <- v[l] + v[l ^ off], off = 32..1: every lane ends with the same sum.
 #pragma unroll

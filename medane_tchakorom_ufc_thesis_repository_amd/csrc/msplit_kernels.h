@@ -207,6 +207,19 @@ int msk_stencil_spmv(int dim, int32_t nx, int32_t ny, int32_t nz, int64_t nrows,
                      const int* stop, hipStream_t s);
 int msk_box_stencil(int dim, int32_t nx, int32_t ny, int32_t nz, int64_t nrows, int lo, int hi, const BoxCoef* cf,
                     int32_t* rowptr, int32_t* col, double* val, hipStream_t s);
+// ---- the variable-coefficient diffusion operator (msplit_k_diffusion.hip)
+// kappa[i] = 1.0 + (double)(splitmix64(first + i + seed) mod 1000) * 0.001, i < n
+int msk_cell_coefficients(double* kappa, int64_t n, uint64_t first, uint64_t seed, hipStream_t s);
+// the box's rows from kappa = [ghost plane below if glo | block | ghost plane above if ghi]; lo <= glo, hi <= ghi
+int msk_box_diffusion(int dim, int32_t nx, int32_t ny, int32_t nz, int64_t nrows, int glo, int ghi, int lo, int hi,
+                      const double* kappa, int32_t* rowptr, int32_t* col, double* val, hipStream_t s);
+// *fail |= 1 unless every off-diagonal entry of the square CSR has its mirror with the same bits
+int msk_csr_sym_check(int32_t nrows, const int32_t* rowptr, const int32_t* col, const double* val, int* fail,
+                      hipStream_t s);
+// the STENCIL storage of a square 3D box CSR: presence bytes and the legs, nleg 7 (blocked or rv[e * stride + row])
+// or 4 (symmetric, blocked); *fail |= 1 for an entry that is no box neighbour's
+int msk_csr_to_rv(int32_t nrows, int32_t nx, int32_t ny, int nleg, int blocked, int64_t stride, const int32_t* rowptr,
+                  const int32_t* col, const double* val, uint8_t* mask, double* rv, int* fail, hipStream_t s);
 int msk_blas1(int op, double* y, const double* x, const double* z, double alpha, int64_t n, hipStream_t s);
 // ---- compressed-basis GMRES (msplit_cgs_basis.hip, F32): the Krylov basis in HBM as float, VV(j) = vb + j*stride (stride a
 // multiple of 1024), its value (double)VV(j)[i] * scale[j]; all arithmetic f64, DBR lane map and order.

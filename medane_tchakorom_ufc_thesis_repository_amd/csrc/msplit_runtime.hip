@@ -1344,6 +1344,133 @@ extern "C" int msp_mat_create_box_stencil(msp_ctx* c, int dim, int32_t nx, int32
   return msp_mat_create_box_stencil_ext(c, dim, nx, ny, nz, 0, 0, out);
 }
 
+// rv_attach for a square 3D box CSR that is already in HBM (msp_mat_create_box_diffusion): the same conditions,
+// layouts and decisions, with the two O(n) passes -- the symmetry test and the scatter of the entries to the legs --
+// as kernels over the device CSR (msk_csr_sym_check, msk_csr_to_rv), so no host array grows with n; two flags come
+// back.  The shape conditions are box_dictionary's on the seven offsets {0, -+1, -+nx, -+nx ny}, which a box of
+// nx, ny > 1 and two planes or more holds all of (one plane has five: rv_attach reads that as 2D and keeps CSR).
+static int rv_attach_device(msp_mat* A, int32_t nx, int32_t ny, int32_t nz) {
+  msp_ctx* c = A->ctx;
+  const int32_t n = A->nrows;
+  if (n == 0 || A->ncols != n || A->dv_on || nx <= 1 || ny <= 1 || nz <= 1 || !msk_march_chunk_fits(nx, ny, 0))
+    return MSP_SUCCESS;
+  const int64_t stride = ((int64_t)n + 511) / 512 * 512;
+  const char* lay = getenv("MSPLIT_RV_LAYOUT");
+  const bool blocked = !(lay && strcmp(lay, "soa") == 0) && n % MSK_DBR_CHUNK == 0;
+  const char* syme = getenv("MSPLIT_RV_SYM");
+  bool sym = blocked && nx <= 1024 && !(syme && syme[0] == '0');
+  int* fail = reinterpret_cast<int*>(mspi_dev_scratch(c));
+  int hfail = 0;
+  if (sym) {  // decided from the assembled values, as rv_attach does
+    HIPCHK(hipMemsetAsync(fail, 0, sizeof(int), c->stream));
+    KCHK(msk_csr_sym_check(n, A->rowptr, A->col, A->val, fail, c->stream));
+    HIPCHK(hipMemcpyAsync(&hfail, fail, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    sym = hfail == 0;
+  }
+  const int nleg = sym ? 4 : 7;
+  const size_t need = (size_t)n + 16 + (size_t)nleg * stride * sizeof(double);
+  size_t fr = 0, tot = 0;
+  if (mspi_mem_info(c, &fr, &tot) || fr < need + (tot >> 5)) {  // keep 1/32 of HBM free after it
+    (void)hipGetLastError();
+    return MSP_SUCCESS;
+  }
+  auto drop = [&]() {
+    rv_free(A);
+    if (A->march_mask) (void)hipFree(A->march_mask);
+    A->march_mask = nullptr;
+  };
+  if (mspi_big_alloc((void**)&A->march_mask, (size_t)n + 16) != (int)hipSuccess ||
+      mspi_big_alloc((void**)&A->rv_val, (size_t)nleg * stride * sizeof(double)) != (int)hipSuccess) {
+    (void)hipGetLastError();  // the allocation failure is not the caller's error: the matrix stays in CSR
+    drop();
+    return MSP_SUCCESS;
+  }
+  HIPCHK(hipMemsetAsync(A->march_mask + n, 0, 16, c->stream));
+  HIPCHK(hipMemsetAsync(fail, 0, sizeof(int), c->stream));
+  KCHK(msk_csr_to_rv(n, nx, ny, nleg, blocked ? 1 : 0, stride, A->rowptr, A->col, A->val, A->march_mask, A->rv_val, fail,
+                     c->stream));
+  KCHK(msk_march_check(n, nx, ny, 0, A->march_mask, fail, c->stream));
+  HIPCHK(hipMemcpyAsync(&hfail, fail, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (hfail) {
+    drop();
+    return MSP_SUCCESS;
+  }
+  A->rv_stride = sym ? -1 : blocked ? 0 : stride;
+  A->march_nx = nx;
+  A->march_ny = ny;
+  A->march_nz = nz;
+  A->march_d2 = 0;
+  A->march_halo = 0;
+  A->rv_on = dv_default();
+  return MSP_SUCCESS;
+}
+
+extern "C" int msp_mat_create_box_diffusion(msp_ctx* c, int dim, int32_t nx, int32_t ny, int32_t nz, int32_t ghost_lo,
+                                            int32_t ghost_hi, int32_t lo, int32_t hi, const msp_vec* kappa,
+                                            msp_mat** out) {
+  ARGCHK(c && out && kappa, MSP_ERR_ARG_NULL, "NULL argument");
+  *out = nullptr;
+  ARGCHK(dim == 2 || dim == 3, MSP_ERR_ARG_OUTOFRANGE, "dim must be 2 or 3, got %d", dim);
+  ARGCHK(nx > 0 && ny > 0 && nz > 0, MSP_ERR_ARG_OUTOFRANGE, "box %d x %d x %d: every extent must be positive", nx, ny,
+         nz);
+  ARGCHK(dim == 3 || nz == 1, MSP_ERR_ARG_OUTOFRANGE, "a 2D box has nz = 1, got %d", nz);
+  ARGCHK((ghost_lo == 0 || ghost_lo == 1) && (ghost_hi == 0 || ghost_hi == 1) && (lo == 0 || lo == 1) &&
+             (hi == 0 || hi == 1),
+         MSP_ERR_ARG_OUTOFRANGE, "ghost_lo %d, ghost_hi %d, lo %d, hi %d: each flag is 0 or 1", ghost_lo, ghost_hi, lo,
+         hi);
+  ARGCHK(lo <= ghost_lo, MSP_ERR_ARG_OUTOFRANGE, "lo = 1 keeps the columns of a plane below that ghost_lo = 0 says "
+         "does not exist");
+  ARGCHK(hi <= ghost_hi, MSP_ERR_ARG_OUTOFRANGE, "hi = 1 keeps the columns of a plane above that ghost_hi = 0 says "
+         "does not exist");
+  const int64_t nrows = (int64_t)nx * ny * nz;
+  const int64_t plane = dim == 3 ? (int64_t)nx * ny : (int64_t)nx;
+  const int64_t ncols = nrows + (lo + hi) * plane;
+  const int64_t deg = dim == 3 ? 7 : 5;
+  ARGCHK(ncols <= INT32_MAX && deg * nrows <= INT32_MAX, MSP_ERR_ARG_OUTOFRANGE,
+         "box of %lld rows exceeds 32-bit PetscInt indexing", (long long)nrows);
+  ARGCHK(kappa->ctx == c, MSP_ERR_ARG_WRONG, "kappa belongs to another context");
+  const int64_t nk = nrows + (ghost_lo + ghost_hi) * plane;
+  ARGCHK(kappa->n == nk, MSP_ERR_ARG_SIZ, "kappa holds %lld coefficients, the box with its ghost planes %lld cells",
+         (long long)kappa->n, (long long)nk);
+  msp_mat* A = new msp_mat();
+  A->ctx = c;
+  mspi_ctx_retain(c);
+  A->nrows = (int32_t)nrows;
+  A->ncols = (int32_t)ncols;
+  // exact nnz, as msp_mat_create_box_convdiff: the structure is the box stencil's
+  int64_t nnz = deg * nrows - 2 * (nrows / nx) - 2 * (nrows / ny);
+  if (dim == 3) nnz -= 2 * (nrows / nz);
+  nnz += (lo + hi) * plane;
+  A->nnz = nnz;
+  A->lds_cap = lds_cap_for(deg * 256);
+  A->lds_cap512 = lds_cap_for(deg * 512);
+  A->plane = dim == 3 ? plane : 0;
+  int rc = mat_alloc(c, A, nrows + 1, nnz);
+  if (rc) {
+    msp_mat_destroy(&A);
+    return rc;
+  }
+  {  // on a HIP failure A is destroyed, which also drops its reference on the context
+    const int e1 = msk_box_diffusion(dim, nx, ny, nz, nrows, ghost_lo, ghost_hi, lo, hi, kappa->d, A->rowptr, A->col,
+                                     A->val, c->stream);
+    const int e2 = e1 ? 0 : (int)hipStreamSynchronize(c->stream);
+    if (e1 || e2) {
+      msp_mat_destroy(&A);
+      mspi_set_error(MSP_ERR_LIB, "box diffusion assembly failed: %s", hipGetErrorString((hipError_t)(e1 ? e1 : e2)));
+      return MSP_ERR_LIB;
+    }
+  }
+  // per-row values: no dictionary is attempted; the square 3D block takes the STENCIL storage where it qualifies
+  if (dim == 3 && !lo && !hi && (rc = rv_attach_device(A, nx, ny, nz))) {
+    msp_mat_destroy(&A);
+    return rc;
+  }
+  *out = A;
+  return MSP_SUCCESS;
+}
+
 extern "C" int msp_mat_destroy(msp_mat** pA) {
   if (!pA || !*pA) return MSP_SUCCESS;
   msp_mat* A = *pA;
@@ -2068,6 +2195,15 @@ extern "C" int msp_vec_set(msp_vec* v, double a) {
   int rc = vec_ok(v, "v");
   if (rc) return rc;
   return mspi_set(v->ctx, v->d, v->n, a);
+}
+
+extern "C" int msp_vec_set_cell_coefficients(msp_vec* kappa, int64_t first_cell, uint64_t seed) {
+  int rc = vec_ok(kappa, "kappa");
+  if (rc) return rc;
+  if (kappa->n == 0) return MSP_SUCCESS;
+  KTimer kt(kappa->ctx, MSP_KERNEL_OTHER, 8.0 * (double)kappa->n);
+  KCHK(msk_cell_coefficients(kappa->d, kappa->n, (uint64_t)first_cell, seed, kappa->ctx->stream));
+  return MSP_SUCCESS;
 }
 
 extern "C" int msp_vec_copy(const msp_vec* x, msp_vec* y) {

@@ -13,7 +13,10 @@ Options are the reference's: -m (mesh lines) -n (mesh columns) -s -npb -rtol
 and the inner/outer solvers' -inner{b}_ksp_* / -outer{b}_ksp_* keys.  The
 drivers are 2D like the reference's; -dim 3 -p <planes> selects the 3D 7-point
 operator (m x n x p, z-slabs) and -peclet px,py,pz the convection-diffusion
-one.  -npb must be 1 (one GPU per block).
+one.  -kappa_seed S selects the variable-coefficient diffusion operator
+-div(kappa grad u) with the hashed per-cell field of seed S (assembled on the
+device, Mat.box_diffusion), in every program; not together with a non-zero
+-peclet or -msplit_operator matfree.  -npb must be 1 (one GPU per block).
 
 Blocks: one per rank under torch.distributed.run (nccl = RCCL when GPUs are
 visible, else gloo), or -nb <blocks> in one process (round-robin on one GPU).
@@ -51,7 +54,7 @@ def parse(argv):
         "npb": opts.get_int("npb", 1), "rtol": opts.get_real("rtol", 1e-6), "atol": opts.get_real("atol", 1e-100),
         "dim": opts.get_int("dim", 2), "p": opts.get_int("p", 0), "nb": opts.get_int("nb", 0),
         "max_outer": opts.get_int("max_outer", 100000), "json": opts.get_bool("json", False),
-        "peclet": None,
+        "peclet": None, "kappa_seed": opts.get_int("kappa_seed", None),
     }
     pe = opts.get_string("peclet", None)
     if pe is not None:
@@ -133,7 +136,7 @@ def run(argv) -> dict:
         ids = list(range(nb))
     from .multisplitting import make_blocks, smsm_local_solve, smsm_semi_local_solve, smsm_solve, sm_solve, \
         GpuMinimizer
-    blocks = make_blocks(ctx, dim, nx, ny, nz, nb, ids, opts, comm, p["peclet"])
+    blocks = make_blocks(ctx, dim, nx, ny, nz, nb, ids, opts, comm, p["peclet"], p["kappa_seed"])
     s, rtol, atol = p["s"], p["rtol"], p["atol"]
     if kind == "sm":
         r = sm_solve(blocks, comm, rtol, atol, p["max_outer"])
@@ -180,10 +183,19 @@ def _gmres(ctx, opts, p):
     import time
     from .petsc import KSP, Mat, Vec
     dim, nx, ny, nz = p["dim"], p["m"], p["n"], p["p"] or 1
-    if dim == 2:       # poisson2DMatrix numbering: m lines of n columns -> box (n fast, m slow)
-        A = Mat.box_convdiff(ctx, 2, ny, nx, 1, False, False, p["peclet"] or (0.0, 0.0, 0.0))
+    box = (2, ny, nx, 1) if dim == 2 else (3, nx, ny, nz)   # 2D, poisson2DMatrix numbering: n fast, m slow
+    if p["kappa_seed"] is not None:
+        from .petsc import PETSC_ERR_ARG_INCOMP, PETSC_ERR_SUP, MsplitError
+        if p["peclet"] is not None and any(v != 0.0 for v in p["peclet"]):
+            raise MsplitError(PETSC_ERR_ARG_INCOMP, "-kappa_seed and a non-zero -peclet name two operators")
+        if opts.get_string("msplit_operator", "csr") == "matfree":
+            raise MsplitError(PETSC_ERR_SUP, "-msplit_operator matfree with -kappa_seed: the diffusion operator has "
+                              "no matrix-free form")
+        kap = Vec(ctx, box[1] * box[2] * box[3])
+        kap.set_cell_coefficients(0, p["kappa_seed"])
+        A = Mat.box_diffusion(ctx, *box, False, False, kap)
     else:
-        A = Mat.box_convdiff(ctx, 3, nx, ny, nz, False, False, p["peclet"] or (0.0, 0.0, 0.0))
+        A = Mat.box_convdiff(ctx, *box, False, False, p["peclet"] or (0.0, 0.0, 0.0))
     n = A.shape[0]
     u = Vec(ctx, n)
     u.set(1.0)

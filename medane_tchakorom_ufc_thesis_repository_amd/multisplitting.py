@@ -22,8 +22,33 @@ import os
 import time
 from dataclasses import dataclass, field
 
-from .petsc import PETSC_ERR_ARG_OUTOFRANGE, Context, DenseMat, Mat, MsplitError, Options, Vec
+from .petsc import PETSC_ERR_ARG_OUTOFRANGE, PETSC_ERR_SUP, Context, DenseMat, Mat, MsplitError, Options, Vec
 from .utils import BlockLayout, block_layout, initializeKSP, initializeOuterKSP, inner_solver, updateLocalRHS
+
+
+def kappa_vec(ctx: Context, layout: BlockLayout, ghost_lo: bool, ghost_hi: bool) -> Vec:
+    """The diffusion operator's coefficients of a block in HBM, [ghost plane below | the block | ghost plane above]:
+    filled on the device for a seeded field, uploaded for a callable (utils.kappa_field)."""
+    first, count = layout.kappa_cells(ghost_lo, ghost_hi)
+    kap = Vec(ctx, count)
+    seed = getattr(layout.kappa, "seed", None)
+    if seed is not None:
+        kap.set_cell_coefficients(first, seed)
+    else:
+        kap.set_values(layout.kappa(first, count))
+    return kap
+
+
+def box_operator(ctx: Context, layout: BlockLayout, lo: bool, hi: bool) -> Mat:
+    """A block's rows assembled on the device, the columns of the plane below / above kept with lo / hi: the
+    diffusion operator (Mat.box_diffusion) when the layout carries a kappa -- the ghost planes are the neighbour
+    blocks' boundary planes, whose kappa the block's face weights read whether or not their columns are kept --,
+    else Poisson / convection-diffusion (Mat.box_convdiff)."""
+    if getattr(layout, "kappa", None) is None:
+        return Mat.box_convdiff(ctx, *layout.box, lo, hi, tuple(getattr(layout, "peclet", (0.0, 0.0, 0.0))))
+    ghost_lo, ghost_hi = layout.b > 0, layout.b < layout.nb - 1
+    kap = kappa_vec(ctx, layout, ghost_lo, ghost_hi)
+    return Mat.box_diffusion(ctx, *layout.box, lo, hi, kap, ghost_lo=ghost_lo, ghost_hi=ghost_hi)
 
 
 class GpuBlock:
@@ -41,9 +66,12 @@ class GpuBlock:
         self.peclet = tuple(getattr(layout, "peclet", (0.0, 0.0, 0.0)))
         # -msplit_operator matfree: A_ii applied without storage (bitwise the assembled products)
         if opts is not None and opts.get_string("msplit_operator", "csr") == "matfree":
+            if getattr(layout, "kappa", None) is not None:
+                raise MsplitError(PETSC_ERR_SUP, "-msplit_operator matfree with kappa (-kappa_seed): the diffusion "
+                                  "operator has no matrix-free form")
             self.A = Mat.box_matfree(ctx, dim, bx, by, bz, False, False, self.peclet)
         else:
-            self.A = Mat.box_convdiff(ctx, dim, bx, by, bz, False, False, self.peclet)
+            self.A = box_operator(ctx, layout, False, False)
         # DV storage holds the operator in ~1 byte per entry; its CSR copy is freed unless -msplit_keep_csr
         self._release_csr = not (opts is not None and opts.get_bool("msplit_keep_csr", False))
         self.prefix = prefix if prefix is not None else f"inner{layout.b + 1}_"
@@ -160,8 +188,7 @@ class GpuBlock:
         self.lo_rows = L.plane if any(nbr < L.b for nbr, *_ in L.recv) else 0
         self.hi_rows = L.plane if any(nbr > L.b for nbr, *_ in L.recv) else 0
         dim, bx, by, bz = L.box
-        self.A_ext = Mat.box_convdiff(self.ctx, dim, bx, by, bz, self.lo_rows > 0, self.hi_rows > 0,
-                                      getattr(self, "peclet", (0.0, 0.0, 0.0)))
+        self.A_ext = box_operator(self.ctx, L, self.lo_rows > 0, self.hi_rows > 0)
         self._maybe_release_csr(self.A_ext)
 
     def _maybe_release_csr(self, M):
@@ -271,13 +298,13 @@ class GpuBlock:
                 self.R_rep.append(self.R)
                 self.b_all.append(self.b)
                 continue
-            Lj = block_layout(L.dim, L.nx, L.ny, L.nz, L.nb, j, L.peclet)
+            Lj = block_layout(L.dim, L.nx, L.ny, L.nz, L.nb, j, L.peclet, getattr(L, "kappa", None))
             R = DenseMat(self.ctx, Lj.nrows, self.s, self.r_precision)
             R.zero_entries()
             self.R_rep.append(R)
             lo = any(nbr < j for nbr, *_ in Lj.recv)
             hi = any(nbr > j for nbr, *_ in Lj.recv)
-            A = Mat.box_convdiff(self.ctx, *Lj.box, lo, hi, L.peclet)   # b_j = A_block_j 1 (utils.c:623-650)
+            A = box_operator(self.ctx, Lj, lo, hi)                      # b_j = A_block_j 1 (utils.c:623-650)
             ones = Vec(self.ctx, (Lj.plane if lo else 0) + Lj.nrows + (Lj.plane if hi else 0))
             ones.set(1.0)
             bj = Vec(self.ctx, Lj.nrows)
@@ -552,9 +579,10 @@ def smsm_solve(blocks, comm, s: int, minimizer, rtol: float, atol: float = 1e-10
     return res
 
 
-def make_blocks(ctx: Context, dim, nx, ny, nz, nb, block_ids, opts: Options | None, comm, peclet=None):
-    """GpuBlocks of the Poisson operator, or (peclet) the upwind convection-diffusion one."""
-    return [GpuBlock(ctx, block_layout(dim, nx, ny, nz, nb, b, peclet), opts, comm) for b in block_ids]
+def make_blocks(ctx: Context, dim, nx, ny, nz, nb, block_ids, opts: Options | None, comm, peclet=None, kappa=None):
+    """GpuBlocks of the Poisson operator, (peclet) the upwind convection-diffusion one, or (kappa: a seed of the
+    hashed field or a callable, utils.block_layout) the variable-coefficient diffusion one."""
+    return [GpuBlock(ctx, block_layout(dim, nx, ny, nz, nb, b, peclet, kappa), opts, comm) for b in block_ids]
 
 
 @dataclass
@@ -665,9 +693,10 @@ def smsm_semi_local_solve(blocks, comm, s: int, rtol: float, atol: float = 1e-10
     return res
 
 
-def make_smsm(ctx: Context, dim, nx, ny, nz, nb, block_ids, s: int, opts: Options | None, comm, peclet=None):
+def make_smsm(ctx: Context, dim, nx, ny, nz, nb, block_ids, s: int, opts: Options | None, comm, peclet=None,
+              kappa=None):
     """GpuBlocks with the minimization storage, and the GpuMinimizer over them."""
-    blocks = make_blocks(ctx, dim, nx, ny, nz, nb, block_ids, opts, comm, peclet)
+    blocks = make_blocks(ctx, dim, nx, ny, nz, nb, block_ids, opts, comm, peclet, kappa)
     for blk in blocks:
         blk.setup_minimization(s)
     return blocks, GpuMinimizer(ctx, blocks, comm, opts)

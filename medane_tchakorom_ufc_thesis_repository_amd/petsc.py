@@ -21,6 +21,7 @@ from ._lib import KspOpts, LsqrOpts, MsplitError, call
 PETSC_ERR_SUP = 56
 PETSC_ERR_ARG_WRONG = 62
 PETSC_ERR_ARG_OUTOFRANGE = 63
+PETSC_ERR_ARG_INCOMP = 75
 
 
 def _dp(a: np.ndarray):
@@ -207,6 +208,11 @@ class Vec:
     def set(self, alpha: float):                                   # VecSet
         call("msp_vec_set", self.h, float(alpha))
 
+    def set_cell_coefficients(self, first: int, seed: int):
+        """The hashed coefficient field of the diffusion operator, kappa(c) for the global cells first + i, written on
+        the device (msp_vec_set_cell_coefficients): the bits of utils.cell_coefficients(first, n, seed)."""
+        call("msp_vec_set_cell_coefficients", self.h, int(first), int(seed) & 0xFFFFFFFFFFFFFFFF)
+
     def copy(self, y: "Vec"):                                      # VecCopy(self, y)
         call("msp_vec_copy", self.h, y.h)
 
@@ -318,6 +324,19 @@ class Mat:
         h = C.c_void_p()
         call("msp_mat_create_box_convdiff", ctx.h, int(dim), int(nx), int(ny), int(nz), 1 if lo else 0,
              1 if hi else 0, _dp(pe), C.byref(h))
+        return cls(ctx, h)
+
+    @classmethod
+    def box_diffusion(cls, ctx: Context, dim: int, nx: int, ny: int, nz: int, lo: bool, hi: bool, kappa: Vec,
+                      ghost_lo: bool | None = None, ghost_hi: bool | None = None) -> "Mat":
+        """-div(kappa grad u) on the box, assembled on the device from the per-cell coefficients kappa =
+        [ghost plane below | the block's planes | ghost plane above] (msp_mat_create_box_diffusion); ghost_lo /
+        ghost_hi (default lo / hi) say whether those planes exist, lo / hi whether their columns are kept."""
+        ghost_lo = lo if ghost_lo is None else ghost_lo
+        ghost_hi = hi if ghost_hi is None else ghost_hi
+        h = C.c_void_p()
+        call("msp_mat_create_box_diffusion", ctx.h, int(dim), int(nx), int(ny), int(nz), int(ghost_lo), int(ghost_hi),
+             int(lo), int(hi), kappa.h, C.byref(h))
         return cls(ctx, h)
 
     @classmethod

@@ -13,7 +13,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from .petsc import KSP, LSQR, Context, Mat, Options, Vec
+from .petsc import KSP, LSQR, PETSC_ERR_ARG_INCOMP, Context, Mat, MsplitError, Options, Vec
 
 
 # ------------------------------------------------------------------ dimensions
@@ -64,6 +64,69 @@ def _splitmix64(x):
     return z ^ (z >> np.uint64(31))
 
 
+def cell_coefficients(first: int, count: int, seed: int) -> np.ndarray:
+    """The hashed per-cell coefficient field (build-defined): kappa(c) = 1.0 + (splitmix64(c + seed) mod 1000) * 0.001
+    for the global cells c = first .. first + count, in wrapping 64-bit arithmetic; one multiply, then one add.
+    Vec.set_cell_coefficients writes the same bits on the device."""
+    M = (1 << 64) - 1
+    with np.errstate(over="ignore"):
+        c = np.arange(count, dtype=np.uint64) + np.uint64(int(first) & M)
+        h = _splitmix64(c + np.uint64(int(seed) & M))
+    return 1.0 + (h % np.uint64(1000)).astype(np.float64) * 0.001
+
+
+def diffusion_rows(dim, nx, ny, nz, kappa, ghost_lo, ghost_hi, lo, hi):
+    """The numpy twin of Mat.box_diffusion (msp_mat_create_box_diffusion, include/msplit.h): the rows of
+    -div(kappa grad u) on the nx x ny x nz box (dim 2: nx x ny, nx fastest) from kappa = [ghost plane below if
+    ghost_lo | the block's planes | ghost plane above if ghost_hi].  The face between cells a and b weighs
+    2.0 * ka * kb / (ka + kb), left to right; a face with no cell behind it the cell's own kappa; the diagonal is the
+    sum of the face weights in the order slow-, y-, x-, x+, y+, slow+, the neighbours -weight; lo / hi keep the
+    ghost planes' columns ([plane below | own rows | plane above]).  kappa is not validated.
+    Returns (rowptr int32, col int32, val float64), columns ascending."""
+    if dim not in (2, 3):
+        raise ValueError("dim must be 2 or 3")
+    ghost_lo, ghost_hi, lo, hi = int(ghost_lo), int(ghost_hi), int(lo), int(hi)
+    if lo > ghost_lo or hi > ghost_hi:
+        raise ValueError("lo / hi keep the columns of a ghost plane that does not exist")
+    P = nx * ny if dim == 3 else nx
+    ns = nz if dim == 3 else ny
+    n = P * ns
+    kap = np.ascontiguousarray(kappa, np.float64).ravel()
+    if kap.size != (ghost_lo + ns + ghost_hi) * P:
+        raise ValueError(f"kappa holds {kap.size} coefficients, expected {(ghost_lo + ns + ghost_hi) * P}")
+    l = np.arange(n, dtype=np.int64)
+    g = l + ghost_lo * P
+    i, sl = l % nx, l // P
+    j = (l // nx) % ny
+    ka = kap[g]
+
+    def face(has, off):
+        kb = kap[np.where(has, g + off, g)]
+        with np.errstate(all="ignore"):
+            w = 2.0 * ka * kb / (ka + kb)
+        return np.where(has, w, ka)
+    wsm = face((sl > 0) | bool(ghost_lo), -P)
+    wsp = face((sl < ns - 1) | bool(ghost_hi), P)
+    wxm, wxp = face(i > 0, -1), face(i < nx - 1, 1)
+    e = l + (P if lo else 0)
+    with np.errstate(all="ignore"):
+        if dim == 3:
+            wym, wyp = face(j > 0, -nx), face(j < ny - 1, nx)
+            diag = ((((wsm + wym) + wxm) + wxp) + wyp) + wsp
+            cols = np.stack([e - P, e - nx, e - 1, e, e + 1, e + nx, e + P], axis=1)
+            vals = np.stack([-wsm, -wym, -wxm, diag, -wxp, -wyp, -wsp], axis=1)
+            keep = np.stack([(sl > 0) | bool(lo), j > 0, i > 0, np.ones(n, bool), i < nx - 1, j < ny - 1,
+                             (sl < ns - 1) | bool(hi)], axis=1)
+        else:
+            diag = ((wsm + wxm) + wxp) + wsp
+            cols = np.stack([e - P, e - 1, e, e + 1, e + P], axis=1)
+            vals = np.stack([-wsm, -wxm, diag, -wxp, -wsp], axis=1)
+            keep = np.stack([(sl > 0) | bool(lo), i > 0, np.ones(n, bool), i < nx - 1, (sl < ns - 1) | bool(hi)],
+                            axis=1)
+    rowptr = np.concatenate([[0], np.cumsum(keep.sum(axis=1))]).astype(np.int32)
+    return rowptr, cols[keep].astype(np.int32), vals[keep]
+
+
 def heterogeneous_poisson3d(nx: int, ny: int | None = None, nz: int | None = None, seed: int = 20251121):
     """An assembled AIJ operator with variable coefficients: -div(kappa grad u) on the nx x ny x nz grid (ny, nz
     default to nx), 7 points, in the reference's numbering (x fastest, as poisson3DMatrix, utils.c:30-121).
@@ -78,9 +141,7 @@ def heterogeneous_poisson3d(nx: int, ny: int | None = None, nz: int | None = Non
     nz = nx if nz is None else nz
     P = nx * ny
     N = P * nz
-    with np.errstate(over="ignore"):
-        h = _splitmix64(np.arange(N, dtype=np.uint64) + np.uint64(seed))
-    kap = (1.0 + (h % np.uint64(1000)).astype(np.float64) * 0.001).reshape(nz, ny, nx)   # [k, j, i]
+    kap = cell_coefficients(0, N, seed).reshape(nz, ny, nx)   # [k, j, i]
 
     def face(axis, side):
         nb = np.roll(kap, -side, axis=axis)
@@ -156,6 +217,11 @@ class BlockLayout:
     halo_size: int = 0
     coupling: tuple = ()                        # (row_ids, rowptr, col(halo idx), val)
     peclet: tuple = (0.0, 0.0, 0.0)             # operator: Poisson (0) or upwind convection-diffusion
+    kappa: object = None                        # the diffusion operator's field f(first_cell, count), or None
+
+    def kappa_cells(self, lo: bool, hi: bool):
+        """(first global cell, count) of the coefficient vector [ghost plane below if lo | block | above if hi]."""
+        return self.r0 - (self.plane if lo else 0), self.nrows + (self.plane if lo else 0) + (self.plane if hi else 0)
 
     @property
     def nrows(self):
@@ -185,12 +251,29 @@ def convdiff_coefs(dim, peclet=None):
     return [cm(py), 0.0, cm(px), (4.0 + 2.0 * abs(px)) + 2.0 * abs(py), cp(px), 0.0, cp(py)]
 
 
-def block_layout(dim, nx, ny, nz, nb, b, peclet=None) -> BlockLayout:
+def kappa_field(kappa):
+    """block_layout's kappa argument as a callable f(first_cell, count) -> float64 array: an integer is the seed of
+    the hashed field (cell_coefficients), a callable is the user's own field, None stays None."""
+    if kappa is None or callable(kappa):
+        return kappa
+    seed = int(kappa)
+    f = lambda first, count: cell_coefficients(first, count, seed)
+    f.seed = seed                                # the drivers fill a seeded field on the device
+    return f
+
+
+def block_layout(dim, nx, ny, nz, nb, b, peclet=None, kappa=None) -> BlockLayout:
     """Slab partition of the reference's stencil into nb blocks.
     dim 3: nx x ny x nz grid, block b = planes [b*nz/nb, (b+1)*nz/nb).
     dim 2: m = nx mesh lines x n = ny mesh columns (poisson2DMatrix numbering),
     block b = rows [b*N/nb, (b+1)*N/nb), whole mesh lines only.
-    peclet: the convection-diffusion operator's coupling values instead of -1."""
+    peclet: the convection-diffusion operator's coupling values instead of -1.
+    kappa: the diffusion operator -div(kappa grad u) (diffusion_rows) instead: an integer seed of the hashed field or
+    a callable f(first_cell, count) -> float64 array over the global cell numbering (= the global row numbering);
+    the coupling values are -w of the faces between the block's boundary planes and its neighbours' (kappa_field)."""
+    if kappa is not None and peclet is not None and any(float(v) != 0.0 for v in peclet):
+        raise MsplitError(PETSC_ERR_ARG_INCOMP, "kappa (the diffusion operator) and a non-zero peclet (the "
+                          "convection-diffusion operator) name two operators")
     if dim == 3:
         if nz % nb:
             raise ValueError(f"nz={nz} must be divisible by the number of blocks {nb}")
@@ -224,17 +307,27 @@ def block_layout(dim, nx, ny, nz, nb, b, peclet=None) -> BlockLayout:
     L.halo_size = off
     L.peclet = tuple(peclet) if peclet is not None else (0.0, 0.0, 0.0)
     cf = convdiff_coefs(dim, peclet)
+    L.kappa = kappa_field(kappa)
+
+    def coupling_values(rows, off, const):
+        """-w between the cells of local rows `rows` and their neighbours `off` cells away, or the constant."""
+        if L.kappa is None:
+            return np.full(rows.size, const)
+        ka = np.ascontiguousarray(L.kappa(r0 + int(rows[0]), rows.size), np.float64)
+        kb = np.ascontiguousarray(L.kappa(r0 + int(rows[0]) + off, rows.size), np.float64)
+        with np.errstate(all="ignore"):
+            return -(2.0 * ka * kb / (ka + kb))
     # coupling rows: row l couples to halo lo_off + l (below) and/or hi_off + (l - (nloc-plane)) (above);
     # halo numbering is ascending in global column, so per-row column order is PETSc's.
     ent_r, ent_c, ent_v = [], [], []
     if rows_lo.size:
         ent_r.append(rows_lo)
         ent_c.append(lo_off + rows_lo)
-        ent_v.append(np.full(rows_lo.size, cf[0]))
+        ent_v.append(coupling_values(rows_lo, -plane, cf[0]))
     if rows_hi.size:
         ent_r.append(rows_hi)
         ent_c.append(hi_off + (rows_hi - (nloc - plane)))
-        ent_v.append(np.full(rows_hi.size, cf[6]))
+        ent_v.append(coupling_values(rows_hi, plane, cf[6]))
     if ent_r:
         r = np.concatenate(ent_r)
         c = np.concatenate(ent_c)
