@@ -1040,6 +1040,184 @@ __device__ __forceinline__ void sym_values(const SymTile& st, const double* sux,
   vv[6] = q ? st.own[j][3].y : st.own[j][3].x;
 }
 
+// The chunk-tile kernels' shared pieces.  A workgroup of kT threads owns a DBR chunk tile (4096 rows of a plane,
+// lane t: the row pairs c0 + j * 512 + 2t, +1, j < 8), keeps the window [c0 - nx, c0 + 4096 + nx) of plane z in LDS
+// (sx: the line below first, the own rows from sx + nx, the line above from sx + nx + 4096) and carries its rows
+// of the planes z-1, z, z+1 in registers (xm, xc, xp) while it marches in z.  The layout of the tile, of the
+// window and the order of a row's terms are stated here and nowhere else.
+
+// Workgroup to (tile of the plane, plane group).  xcd1: XCD x (workgroups x, x+8, ...) takes a contiguous eighth of
+// the plane's tiles, so that neighbouring tiles share their halo lines through that XCD's L2; otherwise plane order.
+// REV (xcd & 2): the top plane groups first.
+template <bool REV = true>
+__device__ __forceinline__ void tile_of(int64_t cpp, int32_t nz, int32_t zt, int xcd, int64_t& tile, int64_t& zg) {
+  if (xcd & 1) {
+    const int64_t per = cpp / 8, slot = blockIdx.x / 8;
+    tile = (blockIdx.x % 8) * per + slot % per;
+    zg = slot / per;
+  } else {
+    tile = blockIdx.x % cpp;
+    zg = blockIdx.x / cpp;
+  }
+  if (REV && (xcd & 2)) zg = (nz + zt - 1) / zt - 1 - zg;
+}
+
+// a row pair of a plane that may lie beyond the box (has: it does not): x[0], x[1], or zeros
+__device__ __forceinline__ void pair_or_zero(const double* __restrict__ x, bool has, double& a, double& b) {
+  if (has) {
+    const double2 p2 = *reinterpret_cast<const double2*>(x);
+    a = p2.x;
+    b = p2.y;
+  } else {
+    a = b = 0.0;
+  }
+}
+
+// the presence bytes of a row pair
+__device__ __forceinline__ uint32_t mask_pair(const uint8_t* __restrict__ mask) {
+  return *reinterpret_cast<const uint16_t*>(mask);
+}
+
+// Before the march: xc, the lane's NP row pairs of the first plane (b0: its first pair), and xm, those of the plane
+// marched from (bm), zeros where that lies beyond the box.
+template <int NP>
+__device__ __forceinline__ void planes_first(const double* __restrict__ x, int64_t b0, int64_t bm, bool hasm,
+                                             double (&xc)[2 * NP], double (&xm)[2 * NP]) {
+#pragma unroll
+  for (int j = 0; j < NP; ++j) {
+    pair_or_zero(x + b0 + j * (2 * kT), true, xc[2 * j], xc[2 * j + 1]);
+    pair_or_zero(x + bm + j * (2 * kT), hasm, xm[2 * j], xm[2 * j + 1]);
+  }
+}
+
+// Per plane, issued before the LDS turn-around: xp, the lane's row pairs of the plane marched to (base + dp), and
+// the presence bytes of its rows of this plane.
+template <int NP>
+__device__ __forceinline__ void plane_next(const double* __restrict__ x, const uint8_t* __restrict__ mask,
+                                           int64_t base, int64_t dp, bool hasp, double (&xp)[2 * NP],
+                                           uint32_t (&m)[NP]) {
+#pragma unroll
+  for (int j = 0; j < NP; ++j) {
+    pair_or_zero(x + base + dp + j * (2 * kT), hasp, xp[2 * j], xp[2 * j + 1]);
+    m[j] = mask_pair(mask + base + j * (2 * kT));
+  }
+}
+
+template <int N>
+__device__ __forceinline__ void planes_rotate(double (&xm)[N], double (&xc)[N], const double (&xp)[N]) {
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    xm[i] = xc[i];
+    xc[i] = xp[i];
+  }
+}
+
+// The x window of plane z, as sym_load / sym_store do the leg windows: lane t < nx/2 loads the pair at 2t of the
+// line below the tile and of the line above it (zeros beyond the vector) before the barrier that ends the previous
+// plane's window reads ...
+struct XWin {
+  double2 hl, hh;
+};
+
+__device__ __forceinline__ void xwin_load(XWin& w, const double* __restrict__ x, int64_t c0, int nx, int32_t nz,
+                                          int64_t P, int t) {
+  w.hl = w.hh = make_double2(0.0, 0.0);
+  const bool hasl = t < nx / 2 && c0 - nx >= 0, hash = t < nx / 2 && c0 + kChunk + nx <= (int64_t)nz * P;
+  if (hasl) w.hl = *reinterpret_cast<const double2*>(x + c0 - nx + 2 * t);
+  if (hash) w.hh = *reinterpret_cast<const double2*>(x + c0 + kChunk + 2 * t);
+}
+
+// ... and after it the window is written: the own rows from xc, the two halo pairs, and for nx > 512 the rest of
+// the halo lines.
+__device__ __forceinline__ void xwin_store(const XWin& w, double* sx, const double (&xc)[2 * kIters],
+                                           const double* __restrict__ x, int64_t c0, int nx, int32_t nz, int64_t P,
+                                           int t) {
+#pragma unroll
+  for (int j = 0; j < kIters; ++j)
+    *reinterpret_cast<double2*>(sx + nx + j * (2 * kT) + 2 * t) = make_double2(xc[2 * j], xc[2 * j + 1]);
+  if (t < nx / 2) {
+    *reinterpret_cast<double2*>(sx + 2 * t) = w.hl;
+    *reinterpret_cast<double2*>(sx + nx + kChunk + 2 * t) = w.hh;
+  }
+  for (int i = t + kT; i < nx / 2; i += kT) {
+    *reinterpret_cast<double2*>(sx + 2 * i) =
+        c0 - nx >= 0 ? *reinterpret_cast<const double2*>(x + c0 - nx + 2 * i) : make_double2(0.0, 0.0);
+    *reinterpret_cast<double2*>(sx + nx + kChunk + 2 * i) =
+        c0 + kChunk + nx <= (int64_t)nz * P ? *reinterpret_cast<const double2*>(x + c0 + kChunk + 2 * i)
+                                            : make_double2(0.0, 0.0);
+  }
+}
+
+// The x values of the row at window index e (nx + j * 512 + 2t + q), in column order: z-1, y-1, x-1, d, x+1, y+1,
+// z+1; the two plane neighbours come from the caller's registers, the centre from them or from the window (sx[e]).
+__device__ __forceinline__ void window_x(const double* sx, int e, int nx, double zm, const double& d, double zp,
+                                         double (&xq)[7]) {
+  xq[0] = zm;
+  xq[1] = sx[e - nx];
+  xq[2] = sx[e - 1];
+  xq[3] = d;
+  xq[4] = sx[e + 1];
+  xq[5] = sx[e + nx];
+  xq[6] = zp;
+}
+
+// A row's sum: the terms its presence byte mr names, from 0.0 in column order, vk[k] * (xq[k] * sc).  SCALE false:
+// vk[k] * xq[k] (MatMult and MatResidual on their own).
+template <bool SCALE>
+__device__ __forceinline__ double row_sum(uint32_t mr, const double (&vk)[7], const double (&xq)[7], double sc) {
+  double s = 0.0;
+#pragma unroll
+  for (int k = 0; k < 7; ++k)
+    if (mr & (1u << k)) s = s + vk[k] * (SCALE ? xq[k] * sc : xq[k]);
+  return s;
+}
+
+// a row pair's results, non-temporal (NT) or plain
+template <bool NT>
+__device__ __forceinline__ void store_pair(double* p, double a, double b) {
+  if constexpr (NT) {
+    dx2 o;
+    o.x = a;
+    o.y = b;
+    __builtin_nontemporal_store(o, reinterpret_cast<dx2*>(p));
+  } else {
+    *reinterpret_cast<double2*>(p) = make_double2(a, b);
+  }
+}
+
+// The unmarched pair (one chunk per workgroup, any P, a ragged last chunk): the whole window [lo, lo + wlen) of x,
+// zeros beyond the vector, as 16-byte copies where it is aligned and inside ...
+__device__ __forceinline__ void window_fill(double* sx, const double* __restrict__ x, int64_t lo, int wlen, int64_t n,
+                                            int nx, int t) {
+  if ((nx & 1) == 0 && lo >= 0 && lo + wlen <= n) {
+    const double2* x2 = reinterpret_cast<const double2*>(x + lo);
+    for (int i = t; i < wlen / 2; i += kT) reinterpret_cast<double2*>(sx)[i] = x2[i];
+  } else {
+    for (int i = t; i < wlen; i += kT) {
+      const int64_t r = lo + i;
+      sx[i] = r >= 0 && r < n ? x[r] : 0.0;
+    }
+  }
+}
+
+// ... and per row (base + j * 512 + q; none past n) the presence byte and x(r -+ P) where it names them, issued
+// before the LDS wait.
+__device__ __forceinline__ void gather_planes(const uint8_t* __restrict__ mask, const double* __restrict__ x,
+                                              int64_t base, int64_t n, int64_t P, uint32_t (&m)[2 * kIters],
+                                              double (&xm)[2 * kIters], double (&xp)[2 * kIters]) {
+#pragma unroll
+  for (int j = 0; j < kIters; ++j) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const int64_t r = base + j * (2 * kT) + q;
+      const uint32_t mr = r < n ? (uint32_t)mask[r] : 0u;
+      m[2 * j + q] = mr;
+      xm[2 * j + q] = (mr & 1u) ? x[r - P] : 0.0;
+      xp[2 * j + q] = (mr & 64u) ? x[r + P] : 0.0;
+    }
+  }
+}
+
 // The box march over DBR chunk tiles (planes of whole chunks: P % 4096 == 0), for MatMult, MatResidual
 // and the scaled MatMult on their own: the tiling of k_box_spmv_mdot_march without the dots.  A lane owns
 // 16 rows of the tile (rows 2t, 2t+1 + 512j) and loads x, x(z+1), b and the presence bytes as 16- and
@@ -1066,19 +1244,11 @@ __global__ __launch_bounds__(kT) void k_box_march_chunk(int32_t nx, int64_t P, i
   const int t = threadIdx.x;
   const int64_t cpp = P / kChunk;
   int64_t tile, zg;
-  if (xcd) {  // XCD-contiguous eighths of the plane's tiles (as k_box_spmv_mdot_march)
-    const int64_t per = cpp / 8, slot = blockIdx.x / 8;
-    tile = (blockIdx.x % 8) * per + slot % per;
-    zg = slot / per;
-  } else {
-    tile = blockIdx.x % cpp;
-    zg = blockIdx.x / cpp;
-  }
+  tile_of<false>(cpp, nz, zt, xcd != 0, tile, zg);  // xcd is 0 or 1 here: no reversed order
   const int32_t z0 = (int32_t)zg * zt, z1 = min(z0 + zt, nz);
   const double sc = MODE == MSK_SPMV_SCALED ? *sdev : 1.0;
   double v[7];
   if constexpr (!RV) march_values<false>(dval, v);
-  const int nh = nx / 2;  // double2 per halo line
   double xm[2 * kIters], xc[2 * kIters], xp[2 * kIters];
   double* sux = sx + kChunk + 2 * nx;  // RV == 2: x+1 / y+1 legs of the window [c0 - nx, c0 + 4096)
   double* suy = sux + kChunk + nx;
@@ -1092,14 +1262,15 @@ __global__ __launch_bounds__(kT) void k_box_march_chunk(int32_t nx, int64_t P, i
       uzm[2 * j + 1] = u.y;
     }
   }
-  {
+  {  // planes_first, written out: with the helper this kernel compiles to another occupancy
+     // (profiles/box_tile_helpers/README.md).  halo & 1: the plane below the box is the column space's lo plane
     const int64_t b0 = (int64_t)z0 * P + tile * kChunk + 2 * t;
 #pragma unroll
     for (int j = 0; j < kIters; ++j) {
       const double2 a = *reinterpret_cast<const double2*>(x + b0 + j * (2 * kT));
       xc[2 * j] = a.x;
       xc[2 * j + 1] = a.y;
-      if (z0 > 0 || (halo & 1)) {  // halo & 1: the plane below the box is the column space's lo plane
+      if (z0 > 0 || (halo & 1)) {
         const double2 m2 = *reinterpret_cast<const double2*>(x + b0 - P + j * (2 * kT));
         xm[2 * j] = m2.x;
         xm[2 * j + 1] = m2.y;
@@ -1113,38 +1284,18 @@ __global__ __launch_bounds__(kT) void k_box_march_chunk(int32_t nx, int64_t P, i
     uint32_t m[kIters];
     double2 bb[kIters];
 #pragma unroll
-    for (int j = 0; j < kIters; ++j) {  // plane z+1, b, the presence bytes: issued before the LDS turn-around
-      if (z + 1 < nz || (halo & 2)) {  // halo & 2: the plane above the box is the hi plane
-        const double2 p2 = *reinterpret_cast<const double2*>(x + base + P + j * (2 * kT));
-        xp[2 * j] = p2.x;
-        xp[2 * j + 1] = p2.y;
-      } else {
-        xp[2 * j] = xp[2 * j + 1] = 0.0;
-      }
-      m[j] = *reinterpret_cast<const uint16_t*>(mask + base + j * (2 * kT));
+    for (int j = 0; j < kIters; ++j) {  // plane_next with b's pair behind each of its pairs
+      // halo & 2: the plane above the box is the hi plane
+      pair_or_zero(x + base + P + j * (2 * kT), z + 1 < nz || (halo & 2), xp[2 * j], xp[2 * j + 1]);
+      m[j] = mask_pair(mask + base + j * (2 * kT));
       if constexpr (MODE == MSK_SPMV_RESID) bb[j] = ld_nt(reinterpret_cast<const double2*>(b + base + j * (2 * kT)));
     }
     SymTile st;
     if constexpr (RV == 2) sym_load(st, rv, c0, nx, t);
-    double2 hl = make_double2(0.0, 0.0), hh = make_double2(0.0, 0.0);
-    const bool hasl = t < nh && c0 - nx >= 0, hash = t < nh && c0 + kChunk + nx <= (int64_t)nz * P;
-    if (hasl) hl = *reinterpret_cast<const double2*>(x + c0 - nx + 2 * t);
-    if (hash) hh = *reinterpret_cast<const double2*>(x + c0 + kChunk + 2 * t);
+    XWin xw;
+    xwin_load(xw, x, c0, nx, nz, P, t);
     __syncthreads();  // the previous plane's window reads are done
-#pragma unroll
-    for (int j = 0; j < kIters; ++j)
-      *reinterpret_cast<double2*>(sx + nx + j * (2 * kT) + 2 * t) = make_double2(xc[2 * j], xc[2 * j + 1]);
-    if (t < nh) {
-      *reinterpret_cast<double2*>(sx + 2 * t) = hl;
-      *reinterpret_cast<double2*>(sx + nx + kChunk + 2 * t) = hh;
-    }
-    for (int i = t + kT; i < nh; i += kT) {  // nx > 512: the rest of the halo lines
-      *reinterpret_cast<double2*>(sx + 2 * i) =
-          c0 - nx >= 0 ? *reinterpret_cast<const double2*>(x + c0 - nx + 2 * i) : make_double2(0.0, 0.0);
-      *reinterpret_cast<double2*>(sx + nx + kChunk + 2 * i) =
-          c0 + kChunk + nx <= (int64_t)nz * P ? *reinterpret_cast<const double2*>(x + c0 + kChunk + 2 * i)
-                                              : make_double2(0.0, 0.0);
-    }
+    xwin_store(xw, sx, xc, x, c0, nx, nz, P, t);
     if constexpr (RV == 2) sym_store(st, sux, suy, rv, c0, nx, t);
     __syncthreads();
 #pragma unroll
@@ -1158,45 +1309,20 @@ __global__ __launch_bounds__(kT) void k_box_march_chunk(int32_t nx, int64_t P, i
 #pragma unroll
       for (int q = 0; q < 2; ++q) {
         const int e = j * (2 * kT) + 2 * t + q + nx;
-        const uint32_t mr = (m[j] >> (8 * q)) & 255u;
-        const double xq[7] = {xm[2 * j + q], sx[e - nx], sx[e - 1], xc[2 * j + q], sx[e + 1], sx[e + nx],
-                              xp[2 * j + q]};
-        double vv[7];
-        if constexpr (RV == 2) sym_values(st, sux, suy, uzm[2 * j + q], j, q, e, nx, vv);
-        double s = 0.0;
+        double xq[7], vk[7];
+        window_x(sx, e, nx, xm[2 * j + q], xc[2 * j + q], xp[2 * j + q], xq);
+        if constexpr (RV == 2) sym_values(st, sux, suy, uzm[2 * j + q], j, q, e, nx, vk);
 #pragma unroll
-        for (int k = 0; k < 7; ++k) {
-          const double vk = RV == 2 ? vv[k] : RV ? (q ? rq[k].y : rq[k].x) : v[k];
-          if (mr & (1u << k)) s = s + vk * (MODE == MSK_SPMV_SCALED ? xq[k] * sc : xq[k]);
-        }
-        if constexpr (MODE == MSK_SPMV_RESID) s = (q ? bb[j].y : bb[j].x) - s;
-        o[q] = s;
+        for (int k = 0; k < 7; ++k)
+          if constexpr (RV != 2) vk[k] = RV ? (q ? rq[k].y : rq[k].x) : v[k];
+        const double s = row_sum<MODE == MSK_SPMV_SCALED>((m[j] >> (8 * q)) & 255u, vk, xq, sc);
+        o[q] = MODE == MSK_SPMV_RESID ? (q ? bb[j].y : bb[j].x) - s : s;
       }
       const int64_t r = base + j * (2 * kT);
-      if constexpr (NTY) {
-        dx2 w2;
-        w2.x = o[0];
-        w2.y = o[1];
-        __builtin_nontemporal_store(w2, reinterpret_cast<dx2*>(y + r));
-      } else {
-        *reinterpret_cast<double2*>(y + r) = make_double2(o[0], o[1]);
-      }
-      if (MODE == MSK_SPMV_SCALED && vout) {
-        if constexpr (NTY) {
-          dx2 w2;
-          w2.x = xc[2 * j] * sc;
-          w2.y = xc[2 * j + 1] * sc;
-          __builtin_nontemporal_store(w2, reinterpret_cast<dx2*>(vout + r));
-        } else {
-          *reinterpret_cast<double2*>(vout + r) = make_double2(xc[2 * j] * sc, xc[2 * j + 1] * sc);
-        }
-      }
+      store_pair<NTY>(y + r, o[0], o[1]);
+      if (MODE == MSK_SPMV_SCALED && vout) store_pair<NTY>(vout + r, xc[2 * j] * sc, xc[2 * j + 1] * sc);
     }
-#pragma unroll
-    for (int i = 0; i < 2 * kIters; ++i) {
-      xm[i] = xc[i];
-      xc[i] = xp[i];
-    }
+    planes_rotate(xm, xc, xp);
     if constexpr (RV == 2) {
 #pragma unroll
       for (int j = 0; j < kIters; ++j) {
@@ -1230,32 +1356,13 @@ __global__ __launch_bounds__(kT) void k_box_spmv_mdot(int32_t nx, int64_t P, int
   const int64_t c = blockIdx.x, c0 = c * kChunk, lo = c0 - nx;
   const int64_t base = c0 + 2 * t;
   const bool full = (c + 1) * kChunk <= n;
-  const int wlen = kChunk + 2 * nx;
-  if ((nx & 1) == 0 && lo >= 0 && lo + wlen <= n) {  // 16-byte aligned interior window
-    const double2* x2 = reinterpret_cast<const double2*>(x + lo);
-    for (int i = t; i < wlen / 2; i += kT) reinterpret_cast<double2*>(sx)[i] = x2[i];
-  } else {
-    for (int i = t; i < wlen; i += kT) {
-      const int64_t r = lo + i;
-      sx[i] = r >= 0 && r < n ? x[r] : 0.0;
-    }
-  }
+  window_fill(sx, x, lo, kChunk + 2 * nx, n, nx, t);
   const double sc = *sdev;
   double v[7];
   march_values<D2>(dval, v);
   uint32_t m[2 * kIters];
   double xm[2 * kIters], xp[2 * kIters];
-#pragma unroll
-  for (int j = 0; j < kIters; ++j) {  // presence bytes and the -+plane neighbours, issued before the LDS wait
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const int64_t r = base + j * (2 * kT) + q;
-      const uint32_t mr = r < n ? (uint32_t)mask[r] : 0u;
-      m[2 * j + q] = mr;
-      xm[2 * j + q] = (mr & 1u) ? x[r - P] : 0.0;
-      xp[2 * j + q] = (mr & 64u) ? x[r + P] : 0.0;
-    }
-  }
+  gather_planes(mask, x, base, n, P, m, xm, xp);
   __syncthreads();
   double wr[2 * kIters];
 #pragma unroll
@@ -1263,25 +1370,14 @@ __global__ __launch_bounds__(kT) void k_box_spmv_mdot(int32_t nx, int64_t P, int
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
       const int e = j * (2 * kT) + 2 * t + q + nx;  // the row's place in the window
-      const uint32_t mr = m[2 * j + q];
-      const double xq[7] = {xm[2 * j + q], sx[e - nx], sx[e - 1], sx[e], sx[e + 1], sx[e + nx], xp[2 * j + q]};
-      double s = 0.0;
-#pragma unroll
-      for (int k = 0; k < 7; ++k)
-        if (mr & (1u << k)) s = s + v[k] * (xq[k] * sc);
-      wr[2 * j + q] = s;
+      double xq[7];
+      window_x(sx, e, nx, xm[2 * j + q], sx[e], xp[2 * j + q], xq);
+      wr[2 * j + q] = row_sum<true>(m[2 * j + q], v, xq, sc);
     }
     const int64_t r = base + j * (2 * kT);
     if (!y) continue;  // uniform: the W-free step (k_box_maxpy recomputes W)
     if (full) {
-      if constexpr (NTY) {
-        dx2 o;
-        o.x = wr[2 * j];
-        o.y = wr[2 * j + 1];
-        __builtin_nontemporal_store(o, reinterpret_cast<dx2*>(y + r));
-      } else {
-        *reinterpret_cast<double2*>(y + r) = make_double2(wr[2 * j], wr[2 * j + 1]);
-      }
+      store_pair<NTY>(y + r, wr[2 * j], wr[2 * j + 1]);
     } else {
       if (r < n) y[r] = wr[2 * j];
       if (r + 1 < n) y[r + 1] = wr[2 * j + 1];
@@ -1343,16 +1439,7 @@ __global__ __launch_bounds__(kT) void k_box_spmv_mdot_march(int32_t nx, int64_t 
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
   const int64_t cpp = P / kChunk;
   int64_t tile, zg;
-  if (xcd & 1) {  // XCD x (workgroups x, x+8, ...) takes a contiguous eighth of the plane's tiles: neighbouring
-                  // tiles share their halo lines through that XCD's L2
-    const int64_t per = cpp / 8, slot = blockIdx.x / 8;
-    tile = (blockIdx.x % 8) * per + slot % per;
-    zg = slot / per;
-  } else {
-    tile = blockIdx.x % cpp;
-    zg = blockIdx.x / cpp;
-  }
-  if (xcd & 2) zg = (nz + zt - 1) / zt - 1 - zg;  // top plane groups first
+  tile_of(cpp, nz, zt, xcd, tile, zg);
   const int32_t z0 = (int32_t)zg * zt, z1 = min(z0 + zt, nz);
   // xcd & 4: odd plane groups march down (round 6).  A group reads one plane of x beyond each end of its range (and,
   // RV == 2, the z+1 leg of the plane below): marching up, the plane below at its start and the plane above at its
@@ -1364,7 +1451,6 @@ __global__ __launch_bounds__(kT) void k_box_spmv_mdot_march(int32_t nx, int64_t 
   const double sc = *sdev;
   double v[7];
   if constexpr (!RV) march_values<false>(dval, v);
-  const int nh = nx / 2;  // double2 per halo line
   double xm[2 * kIters], xc[2 * kIters], xp[2 * kIters];
   double* sux = sx + kChunk + 2 * nx;  // RV == 2 (symmetric storage): x+1 / y+1 legs of the window
   double* suy = sux + kChunk + nx;
@@ -1382,19 +1468,7 @@ __global__ __launch_bounds__(kT) void k_box_spmv_mdot_march(int32_t nx, int64_t 
     const int32_t zf = down ? z1 - 1 : z0;
     const bool hasm = down ? z1 < nz : z0 > 0;
     const int64_t b0 = (int64_t)zf * P + tile * kChunk + 2 * t, bm = b0 + (down ? P : -P);
-#pragma unroll
-    for (int j = 0; j < kIters; ++j) {
-      const double2 a = *reinterpret_cast<const double2*>(x + b0 + j * (2 * kT));
-      xc[2 * j] = a.x;
-      xc[2 * j + 1] = a.y;
-      if (hasm) {
-        const double2 m2 = *reinterpret_cast<const double2*>(x + bm + j * (2 * kT));
-        xm[2 * j] = m2.x;
-        xm[2 * j + 1] = m2.y;
-      } else {
-        xm[2 * j] = xm[2 * j + 1] = 0.0;
-      }
-    }
+    planes_first<kIters>(x, b0, bm, hasm, xc, xm);
   }
   for (int32_t zi = 0; zi < z1 - z0; ++zi) {
     const int32_t z = down ? z1 - 1 - zi : z0 + zi;
@@ -1402,17 +1476,7 @@ __global__ __launch_bounds__(kT) void k_box_spmv_mdot_march(int32_t nx, int64_t 
     const bool hasp = down ? z > 0 : z + 1 < nz;  // xp: the plane marched to (z+1 going up, z-1 going down)
     const int64_t dp = down ? -P : P;
     uint32_t m[kIters];
-#pragma unroll
-    for (int j = 0; j < kIters; ++j) {  // the next plane, the presence bytes: issued before the LDS turn-around
-      if (hasp) {
-        const double2 p2 = *reinterpret_cast<const double2*>(x + base + dp + j * (2 * kT));
-        xp[2 * j] = p2.x;
-        xp[2 * j + 1] = p2.y;
-      } else {
-        xp[2 * j] = xp[2 * j + 1] = 0.0;
-      }
-      m[j] = *reinterpret_cast<const uint16_t*>(mask + base + j * (2 * kT));
-    }
+    plane_next<kIters>(x, mask, base, dp, hasp, xp, m);
     // RV: the plane's seven value legs for all the lane's rows, issued with x(z+1) before the LDS turn-around (the
     // kernel runs one workgroup per CU, so the unified register file holds them; loaded after the barrier they
     // were a second, exposed round trip per plane)
@@ -1425,25 +1489,10 @@ __global__ __launch_bounds__(kT) void k_box_spmv_mdot_march(int32_t nx, int64_t 
 #pragma unroll
         for (int k = 0; k < 7; ++k) rqa[j][k] = ld_nt(rv_pair(rv, rvs, c0, k, j, t));
     }
-    double2 hl = make_double2(0.0, 0.0), hh = make_double2(0.0, 0.0);
-    const bool hasl = t < nh && c0 - nx >= 0, hash = t < nh && c0 + kChunk + nx <= (int64_t)nz * P;
-    if (hasl) hl = *reinterpret_cast<const double2*>(x + c0 - nx + 2 * t);
-    if (hash) hh = *reinterpret_cast<const double2*>(x + c0 + kChunk + 2 * t);
+    XWin xw;
+    xwin_load(xw, x, c0, nx, nz, P, t);
     __syncthreads();  // the previous plane's window reads (and its partial writes) are done
-#pragma unroll
-    for (int j = 0; j < kIters; ++j)
-      *reinterpret_cast<double2*>(sx + nx + j * (2 * kT) + 2 * t) = make_double2(xc[2 * j], xc[2 * j + 1]);
-    if (t < nh) {
-      *reinterpret_cast<double2*>(sx + 2 * t) = hl;
-      *reinterpret_cast<double2*>(sx + nx + kChunk + 2 * t) = hh;
-    }
-    for (int i = t + kT; i < nh; i += kT) {  // nx > 512: the rest of the halo lines
-      *reinterpret_cast<double2*>(sx + 2 * i) =
-          c0 - nx >= 0 ? *reinterpret_cast<const double2*>(x + c0 - nx + 2 * i) : make_double2(0.0, 0.0);
-      *reinterpret_cast<double2*>(sx + nx + kChunk + 2 * i) =
-          c0 + kChunk + nx <= (int64_t)nz * P ? *reinterpret_cast<const double2*>(x + c0 + kChunk + 2 * i)
-                                              : make_double2(0.0, 0.0);
-    }
+    xwin_store(xw, sx, xc, x, c0, nx, nz, P, t);
     if constexpr (RV == 2) sym_store(st, sux, suy, rv, c0, nx, t);
     __syncthreads();
     double wr[2 * kIters];
@@ -1458,28 +1507,17 @@ __global__ __launch_bounds__(kT) void k_box_spmv_mdot_march(int32_t nx, int64_t 
 #pragma unroll
       for (int q = 0; q < 2; ++q) {
         const int e = j * (2 * kT) + 2 * t + q + nx;
-        const uint32_t mr = (m[j] >> (8 * q)) & 255u;
-        const double xq[7] = {down ? xp[2 * j + q] : xm[2 * j + q], sx[e - nx], sx[e - 1], xc[2 * j + q],
-                              sx[e + 1], sx[e + nx], down ? xm[2 * j + q] : xp[2 * j + q]};
-        double vv[7];
-        if constexpr (RV == 2) sym_values(st, sux, suy, uzm[2 * j + q], j, q, e, nx, vv);
-        double s = 0.0;
+        double xq[7], vk[7];
+        window_x(sx, e, nx, down ? xp[2 * j + q] : xm[2 * j + q], xc[2 * j + q],
+                 down ? xm[2 * j + q] : xp[2 * j + q], xq);
+        if constexpr (RV == 2) sym_values(st, sux, suy, uzm[2 * j + q], j, q, e, nx, vk);
 #pragma unroll
-        for (int k = 0; k < 7; ++k) {
-          const double vk = RV == 2 ? vv[k] : RV ? (q ? rqa[RV == 1 ? j : 0][k].y : rqa[RV == 1 ? j : 0][k].x) : v[k];
-          if (mr & (1u << k)) s = s + vk * (xq[k] * sc);
-        }
-        wr[2 * j + q] = s;
+        for (int k = 0; k < 7; ++k)
+          if constexpr (RV != 2) vk[k] = RV ? (q ? rqa[RV == 1 ? j : 0][k].y : rqa[RV == 1 ? j : 0][k].x) : v[k];
+        wr[2 * j + q] = row_sum<true>((m[j] >> (8 * q)) & 255u, vk, xq, sc);
       }
       if (!y) continue;  // uniform: W is recomputed by the MAXPY after (k_box_maxpy_march), not stored
-      if constexpr (NTY) {
-        dx2 o;
-        o.x = wr[2 * j];
-        o.y = wr[2 * j + 1];
-        __builtin_nontemporal_store(o, reinterpret_cast<dx2*>(y + base + j * (2 * kT)));
-      } else {
-        *reinterpret_cast<double2*>(y + base + j * (2 * kT)) = make_double2(wr[2 * j], wr[2 * j + 1]);
-      }
+      store_pair<NTY>(y + base + j * (2 * kT), wr[2 * j], wr[2 * j + 1]);
     }
     // self: the last basis vector is x itself, whose rows of this plane the lane holds in xc at exactly
     // its DBR positions: that dot is taken from the registers (8n bytes fewer), the same sum term for term
@@ -1506,11 +1544,7 @@ __global__ __launch_bounds__(kT) void k_box_spmv_mdot_march(int32_t nx, int64_t 
     }
     __syncthreads();
     if (t < nv) partial[t * nchunks + c] = (red[t][0] + red[t][1]) + (red[t][2] + red[t][3]);
-#pragma unroll
-    for (int i = 0; i < 2 * kIters; ++i) {
-      xm[i] = xc[i];
-      xc[i] = xp[i];
-    }
+    planes_rotate(xm, xc, xp);
     if constexpr (RV == 2) {
 #pragma unroll
       for (int j = 0; j < kIters; ++j) {
@@ -1548,15 +1582,7 @@ __global__ __launch_bounds__(2 * kT) void k_box_spmv_mdot_march_sym2(int32_t nx,
   const int j0 = h * H;  // this thread's first row pair
   const int64_t cpp = P / kChunk;
   int64_t tile, zg;
-  if (xcd & 1) {
-    const int64_t per = cpp / 8, slot = blockIdx.x / 8;
-    tile = (blockIdx.x % 8) * per + slot % per;
-    zg = slot / per;
-  } else {
-    tile = blockIdx.x % cpp;
-    zg = blockIdx.x / cpp;
-  }
-  if (xcd & 2) zg = (nz + zt - 1) / zt - 1 - zg;
+  tile_of(cpp, nz, zt, xcd, tile, zg);
   const int32_t z0 = (int32_t)zg * zt, z1 = min(z0 + zt, nz);
   // xcd & 4: odd plane groups march down (as k_box_spmv_mdot_march).  Going down, plane z's z-1 values are the z+1
   // legs of the plane below, the plane marched to: they are loaded with its x (own[.][3] holds them), and its z+1
@@ -1570,20 +1596,14 @@ __global__ __launch_bounds__(2 * kT) void k_box_spmv_mdot_march_sym2(int32_t nx,
     const int32_t zf = down ? z1 - 1 : z0;
     const bool hasm = down ? z1 < nz : z0 > 0;
     const int64_t cb = ((int64_t)(down ? zf : z0 - 1)) * P + tile * kChunk;
-    const int64_t b0 = (int64_t)zf * P + tile * kChunk + 2 * tl, bm = b0 + (down ? P : -P);
+    const int64_t b0 = (int64_t)zf * P + tile * kChunk + 2 * tl + j0 * (2 * kT), bm = b0 + (down ? P : -P);
 #pragma unroll
     for (int jj = 0; jj < H; ++jj) {
-      const int j = j0 + jj;
-      const double2 u = down || z0 > 0 ? ld_nt(rvs_pair(rv, cb, 3, j, tl)) : make_double2(0.0, 0.0);
+      const double2 u = down || z0 > 0 ? ld_nt(rvs_pair(rv, cb, 3, j0 + jj, tl)) : make_double2(0.0, 0.0);
       uzm[2 * jj] = u.x;
       uzm[2 * jj + 1] = u.y;
-      const double2 a = *reinterpret_cast<const double2*>(x + b0 + j * (2 * kT));
-      xc[2 * jj] = a.x;
-      xc[2 * jj + 1] = a.y;
-      const double2 m2 = hasm ? *reinterpret_cast<const double2*>(x + bm + j * (2 * kT)) : make_double2(0.0, 0.0);
-      xm[2 * jj] = m2.x;
-      xm[2 * jj + 1] = m2.y;
     }
+    planes_first<H>(x, b0, bm, hasm, xc, xm);
   }
   for (int32_t zi = 0; zi < z1 - z0; ++zi) {
     const int32_t z = down ? z1 - 1 - zi : z0 + zi;
@@ -1592,22 +1612,17 @@ __global__ __launch_bounds__(2 * kT) void k_box_spmv_mdot_march_sym2(int32_t nx,
     const int64_t dp = down ? -P : P;
     uint32_t m[H];
     double2 own[H][4];  // own[.][3]: the z+1 legs of plane z (up) or of the plane below (down)
+    plane_next<H>(x, mask, base + j0 * (2 * kT), dp, hasp, xp, m);
 #pragma unroll
     for (int jj = 0; jj < H; ++jj) {
       const int j = j0 + jj;
-      if (hasp) {
-        const double2 p2 = *reinterpret_cast<const double2*>(x + base + dp + j * (2 * kT));
-        xp[2 * jj] = p2.x;
-        xp[2 * jj + 1] = p2.y;
-      } else {
-        xp[2 * jj] = xp[2 * jj + 1] = 0.0;
-      }
-      m[jj] = *reinterpret_cast<const uint16_t*>(mask + base + j * (2 * kT));
 #pragma unroll
       for (int k = 0; k < 3; ++k) own[jj][k] = ld_nt(rvs_pair(rv, c0, k, j, tl));
       own[jj][3] = !down ? ld_nt(rvs_pair(rv, c0, 3, j, tl))
                          : hasp ? ld_nt(rvs_pair(rv, c0 - P, 3, j, tl)) : make_double2(0.0, 0.0);
     }
+    // xwin_load / xwin_store and sym_load / sym_store in one: the first half's lanes take the halo pairs of all three
+    // windows under one test, each pair's three stores go out together, and nx <= 512 leaves no rest of a halo line
     double2 hl = make_double2(0.0, 0.0), hh = make_double2(0.0, 0.0), hx = hl, hy = hl;
     const bool hal = h == 0 && tl < nh;
     if (hal && c0 - nx >= 0) {
@@ -1638,27 +1653,16 @@ __global__ __launch_bounds__(2 * kT) void k_box_spmv_mdot_march_sym2(int32_t nx,
 #pragma unroll
       for (int q = 0; q < 2; ++q) {
         const int e = j * (2 * kT) + 2 * tl + q + nx;
-        const uint32_t mr = (m[jj] >> (8 * q)) & 255u;
-        const double xq[7] = {down ? xp[2 * jj + q] : xm[2 * jj + q], sx[e - nx], sx[e - 1], xc[2 * jj + q],
-                              sx[e + 1], sx[e + nx], down ? xm[2 * jj + q] : xp[2 * jj + q]};
+        double xq[7];
+        window_x(sx, e, nx, down ? xp[2 * jj + q] : xm[2 * jj + q], xc[2 * jj + q],
+                 down ? xm[2 * jj + q] : xp[2 * jj + q], xq);
         const double uf = q ? own[jj][3].y : own[jj][3].x;
         const double vv[7] = {down ? uf : uzm[2 * jj + q], suy[e - nx], sux[e - 1], q ? own[jj][0].y : own[jj][0].x,
                               q ? own[jj][1].y : own[jj][1].x, q ? own[jj][2].y : own[jj][2].x,
                               down ? uzm[2 * jj + q] : uf};
-        double s = 0.0;
-#pragma unroll
-        for (int k = 0; k < 7; ++k)
-          if (mr & (1u << k)) s = s + vv[k] * (xq[k] * sc);
-        wr[2 * jj + q] = s;
+        wr[2 * jj + q] = row_sum<true>((m[jj] >> (8 * q)) & 255u, vv, xq, sc);
       }
-      if constexpr (NTY) {
-        dx2 o;
-        o.x = wr[2 * jj];
-        o.y = wr[2 * jj + 1];
-        __builtin_nontemporal_store(o, reinterpret_cast<dx2*>(y + base + j * (2 * kT)));
-      } else {
-        *reinterpret_cast<double2*>(y + base + j * (2 * kT)) = make_double2(wr[2 * jj], wr[2 * jj + 1]);
-      }
+      store_pair<NTY>(y + base + j * (2 * kT), wr[2 * jj], wr[2 * jj + 1]);
       uzm[2 * jj] = own[jj][3].x;  // the next plane's z-1 values (up) or its z+1 values (down)
       uzm[2 * jj + 1] = own[jj][3].y;
     }
@@ -1699,11 +1703,7 @@ __global__ __launch_bounds__(2 * kT) void k_box_spmv_mdot_march_sym2(int32_t nx,
     }
     __syncthreads();
     if (t < nv) partial[t * nchunks + c] = (red[t][0] + red[t][1]) + (red[t][2] + red[t][3]);
-#pragma unroll
-    for (int i = 0; i < 2 * H; ++i) {
-      xm[i] = xc[i];
-      xc[i] = xp[i];
-    }
+    planes_rotate(xm, xc, xp);
   }
 }
 
@@ -1813,6 +1813,11 @@ __device__ __forceinline__ void maxpy_group_apply(double (&u)[2 * kIters], const
 // window, and W = A (sc x) for the lane's 16 rows in u.  NPF is a template parameter so that all of it is one
 // straight run of code (a run-time count puts the vector loads in branches of their own, and the compiler then
 // moves the x(z) loads below them).
+// It keeps its own copy of the tile's pieces.  xwin_load, planes_first and plane_next load under conditions, and the
+// fences below hold an order only inside one basic block, so its loads are written out, unconditional; with
+// xwin_store or row_sum in place of the window stores and the row sum below, the compiler waits for the prefetched
+// vectors at other points (the s_waitcnt vmcnt sequence of the PF = 1 kernels changes), which is what
+// profiles/maxpy_prefetch/ measured the order for (profiles/box_tile_helpers/README.md).
 #define MSK_LOAD_FENCE(p_)                        \
   asm volatile("" : : "v"(p_) : "memory");        \
   __builtin_amdgcn_sched_barrier(0)
@@ -1915,15 +1920,7 @@ __device__ __forceinline__ void box_maxpy_plane(int32_t nx, int64_t P, int32_t n
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
   const int64_t cpp = P / kChunk;
   int64_t tile, zg;
-  if (xcd & 1) {
-    const int64_t per = cpp / 8, slot = blockIdx.x / 8;
-    tile = (blockIdx.x % 8) * per + slot % per;
-    zg = slot / per;
-  } else {
-    tile = blockIdx.x % cpp;
-    zg = blockIdx.x / cpp;
-  }
-  if (xcd & 2) zg = nz - 1 - zg;
+  tile_of(cpp, nz, 1, xcd, tile, zg);
   const int32_t z = (int32_t)zg;
   const int64_t c = (int64_t)z * cpp + tile, c0 = c * kChunk, base = c0 + 2 * t;
   const int jrem = nv & 3;
@@ -1987,14 +1984,7 @@ __device__ __forceinline__ void box_maxpy_plane(int32_t nx, int64_t P, int32_t n
 #pragma unroll
   for (int j = 0; j < kIters; ++j) {
     const double r0 = u[2 * j], r1 = u[2 * j + 1];
-    if constexpr (NTY) {
-      dx2 o;
-      o.x = r0;
-      o.y = r1;
-      __builtin_nontemporal_store(o, reinterpret_cast<dx2*>(wout + base + j * (2 * kT)));
-    } else {
-      *reinterpret_cast<double2*>(wout + base + j * (2 * kT)) = make_double2(r0, r1);
-    }
+    store_pair<NTY>(wout + base + j * (2 * kT), r0, r1);
     acc = acc + r0 * r0;
     acc = acc + r1 * r1;
   }
@@ -2032,86 +2022,34 @@ __global__ __launch_bounds__(kT) void k_box_maxpy_march(int32_t nx, int64_t P, i
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
   const int64_t cpp = P / kChunk;
   int64_t tile, zg;
-  if (xcd & 1) {
-    const int64_t per = cpp / 8, slot = blockIdx.x / 8;
-    tile = (blockIdx.x % 8) * per + slot % per;
-    zg = slot / per;
-  } else {
-    tile = blockIdx.x % cpp;
-    zg = blockIdx.x / cpp;
-  }
-  if (xcd & 2) zg = (nz + zt - 1) / zt - 1 - zg;
+  tile_of(cpp, nz, zt, xcd, tile, zg);
   const int32_t z0 = (int32_t)zg * zt, z1 = min(z0 + zt, nz);
   const double sc = *sdev;
   double v[7];
   march_values<false>(dval, v);
-  const int nh = nx / 2;
   double xm[2 * kIters], xc[2 * kIters], xp[2 * kIters];
   {
     const int64_t b0 = (int64_t)z0 * P + tile * kChunk + 2 * t;
-#pragma unroll
-    for (int j = 0; j < kIters; ++j) {
-      const double2 a = *reinterpret_cast<const double2*>(x + b0 + j * (2 * kT));
-      xc[2 * j] = a.x;
-      xc[2 * j + 1] = a.y;
-      if (z0 > 0) {
-        const double2 m2 = *reinterpret_cast<const double2*>(x + b0 - P + j * (2 * kT));
-        xm[2 * j] = m2.x;
-        xm[2 * j + 1] = m2.y;
-      } else {
-        xm[2 * j] = xm[2 * j + 1] = 0.0;
-      }
-    }
+    planes_first<kIters>(x, b0, b0 - P, z0 > 0, xc, xm);
   }
   const int jrem = nv & 3;
   for (int32_t z = z0; z < z1; ++z) {
     const int64_t c = (int64_t)z * cpp + tile, c0 = c * kChunk, base = c0 + 2 * t;
     uint32_t m[kIters];
-#pragma unroll
-    for (int j = 0; j < kIters; ++j) {
-      if (z + 1 < nz) {
-        const double2 p2 = *reinterpret_cast<const double2*>(x + base + P + j * (2 * kT));
-        xp[2 * j] = p2.x;
-        xp[2 * j + 1] = p2.y;
-      } else {
-        xp[2 * j] = xp[2 * j + 1] = 0.0;
-      }
-      m[j] = *reinterpret_cast<const uint16_t*>(mask + base + j * (2 * kT));
-    }
-    double2 hl = make_double2(0.0, 0.0), hh = make_double2(0.0, 0.0);
-    const bool hasl = t < nh && c0 - nx >= 0, hash = t < nh && c0 + kChunk + nx <= (int64_t)nz * P;
-    if (hasl) hl = *reinterpret_cast<const double2*>(x + c0 - nx + 2 * t);
-    if (hash) hh = *reinterpret_cast<const double2*>(x + c0 + kChunk + 2 * t);
+    plane_next<kIters>(x, mask, base, P, z + 1 < nz, xp, m);
+    XWin xw;
+    xwin_load(xw, x, c0, nx, nz, P, t);
     __syncthreads();  // the previous plane's window reads (and its red reads) are done
-#pragma unroll
-    for (int j = 0; j < kIters; ++j)
-      *reinterpret_cast<double2*>(sx + nx + j * (2 * kT) + 2 * t) = make_double2(xc[2 * j], xc[2 * j + 1]);
-    if (t < nh) {
-      *reinterpret_cast<double2*>(sx + 2 * t) = hl;
-      *reinterpret_cast<double2*>(sx + nx + kChunk + 2 * t) = hh;
-    }
-    for (int i = t + kT; i < nh; i += kT) {
-      *reinterpret_cast<double2*>(sx + 2 * i) =
-          c0 - nx >= 0 ? *reinterpret_cast<const double2*>(x + c0 - nx + 2 * i) : make_double2(0.0, 0.0);
-      *reinterpret_cast<double2*>(sx + nx + kChunk + 2 * i) =
-          c0 + kChunk + nx <= (int64_t)nz * P ? *reinterpret_cast<const double2*>(x + c0 + kChunk + 2 * i)
-                                              : make_double2(0.0, 0.0);
-    }
+    xwin_store(xw, sx, xc, x, c0, nx, nz, P, t);
     __syncthreads();
     double u[2 * kIters];
 #pragma unroll
     for (int j = 0; j < kIters; ++j) {
 #pragma unroll
       for (int q = 0; q < 2; ++q) {
-        const int e = j * (2 * kT) + 2 * t + q + nx;
-        const uint32_t mr = (m[j] >> (8 * q)) & 255u;
-        const double xq[7] = {xm[2 * j + q], sx[e - nx], sx[e - 1], xc[2 * j + q], sx[e + 1], sx[e + nx],
-                              xp[2 * j + q]};
-        double s = 0.0;
-#pragma unroll
-        for (int k = 0; k < 7; ++k)
-          if (mr & (1u << k)) s = s + v[k] * (xq[k] * sc);
-        u[2 * j + q] = s;
+        double xq[7];
+        window_x(sx, j * (2 * kT) + 2 * t + q + nx, nx, xm[2 * j + q], xc[2 * j + q], xp[2 * j + q], xq);
+        u[2 * j + q] = row_sum<true>((m[j] >> (8 * q)) & 255u, v, xq, sc);
       }
     }
     // u -= sum_j h_j VV(j): leading nv & 3 vectors, then groups of four; VV(nv - 1) = x from xc
@@ -2136,14 +2074,7 @@ __global__ __launch_bounds__(kT) void k_box_maxpy_march(int32_t nx, int64_t P, i
 #pragma unroll
     for (int j = 0; j < kIters; ++j) {
       const double r0 = u[2 * j], r1 = u[2 * j + 1];
-      if constexpr (NTY) {
-        dx2 o;
-        o.x = r0;
-        o.y = r1;
-        __builtin_nontemporal_store(o, reinterpret_cast<dx2*>(wout + base + j * (2 * kT)));
-      } else {
-        *reinterpret_cast<double2*>(wout + base + j * (2 * kT)) = make_double2(r0, r1);
-      }
+      store_pair<NTY>(wout + base + j * (2 * kT), r0, r1);
       acc = acc + r0 * r0;
       acc = acc + r1 * r1;
     }
@@ -2151,11 +2082,7 @@ __global__ __launch_bounds__(kT) void k_box_maxpy_march(int32_t nx, int64_t P, i
     if (lane == 0) red[wv] = acc;
     __syncthreads();
     if (t == 0) partial[c] = (red[0] + red[1]) + (red[2] + red[3]);
-#pragma unroll
-    for (int i = 0; i < 2 * kIters; ++i) {
-      xm[i] = xc[i];
-      xc[i] = xp[i];
-    }
+    planes_rotate(xm, xc, xp);
   }
 }
 
@@ -2215,32 +2142,13 @@ __global__ __launch_bounds__(kT) void k_box_maxpy(int32_t nx, int64_t P, int64_t
   const int64_t c = blockIdx.x, c0 = c * kChunk, lo = c0 - nx;
   const int64_t base = c0 + 2 * t;
   const bool full = (c + 1) * kChunk <= n;
-  const int wlen = kChunk + 2 * nx;
-  if ((nx & 1) == 0 && lo >= 0 && lo + wlen <= n) {
-    const double2* x2 = reinterpret_cast<const double2*>(x + lo);
-    for (int i = t; i < wlen / 2; i += kT) reinterpret_cast<double2*>(sx)[i] = x2[i];
-  } else {
-    for (int i = t; i < wlen; i += kT) {
-      const int64_t r = lo + i;
-      sx[i] = r >= 0 && r < n ? x[r] : 0.0;
-    }
-  }
+  window_fill(sx, x, lo, kChunk + 2 * nx, n, nx, t);
   const double sc = *sdev;
   double v[7];
   march_values<D2>(dval, v);
   uint32_t m[2 * kIters];
   double xm[2 * kIters], xp[2 * kIters];
-#pragma unroll
-  for (int j = 0; j < kIters; ++j) {
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const int64_t r = base + j * (2 * kT) + q;
-      const uint32_t mr = r < n ? (uint32_t)mask[r] : 0u;
-      m[2 * j + q] = mr;
-      xm[2 * j + q] = (mr & 1u) ? x[r - P] : 0.0;
-      xp[2 * j + q] = (mr & 64u) ? x[r + P] : 0.0;
-    }
-  }
+  gather_planes(mask, x, base, n, P, m, xm, xp);
   __syncthreads();
   double u[2 * kIters], xs[2 * kIters];
 #pragma unroll
@@ -2248,13 +2156,9 @@ __global__ __launch_bounds__(kT) void k_box_maxpy(int32_t nx, int64_t P, int64_t
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
       const int e = j * (2 * kT) + 2 * t + q + nx;
-      const uint32_t mr = m[2 * j + q];
-      const double xq[7] = {xm[2 * j + q], sx[e - nx], sx[e - 1], sx[e], sx[e + 1], sx[e + nx], xp[2 * j + q]};
-      double s = 0.0;
-#pragma unroll
-      for (int k = 0; k < 7; ++k)
-        if (mr & (1u << k)) s = s + v[k] * (xq[k] * sc);
-      u[2 * j + q] = s;
+      double xq[7];
+      window_x(sx, e, nx, xm[2 * j + q], sx[e], xp[2 * j + q], xq);
+      u[2 * j + q] = row_sum<true>(m[2 * j + q], v, xq, sc);
       xs[2 * j + q] = sx[e];
     }
   }
@@ -2276,14 +2180,7 @@ __global__ __launch_bounds__(kT) void k_box_maxpy(int32_t nx, int64_t P, int64_t
 #pragma unroll
     for (int j = 0; j < kIters; ++j) {
       const double r0 = u[2 * j], r1 = u[2 * j + 1];
-      if constexpr (NTY) {
-        dx2 o;
-        o.x = r0;
-        o.y = r1;
-        __builtin_nontemporal_store(o, reinterpret_cast<dx2*>(wout + base + j * (2 * kT)));
-      } else {
-        *reinterpret_cast<double2*>(wout + base + j * (2 * kT)) = make_double2(r0, r1);
-      }
+      store_pair<NTY>(wout + base + j * (2 * kT), r0, r1);
       acc = acc + r0 * r0;
       acc = acc + r1 * r1;
     }
@@ -2687,6 +2584,29 @@ static bool march_chunk_ok(int32_t nx, int32_t ny, int d2) {
 // 2 = the symmetric storage (rvs < 0)
 static int rv_form(const double* rv, int64_t rvs) { return !rv ? 0 : rvs < 0 ? 2 : 1; }
 
+static bool a16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// LDS bytes of a chunk tile's x window; sym: the symmetric storage adds the x+1 / y+1 legs' windows
+// (2 x (4096 + nx) doubles; nx <= 1024: <= 128 KiB in all)
+static size_t window_lds(int32_t nx, bool sym) {
+  return (size_t)(kChunk + 2 * nx + (sym ? 2 * (kChunk + nx) : 0)) * sizeof(double);
+}
+
+// The launch geometry of the chunk-tile kernels: a workgroup per tile of a plane and group of zt planes; xcd1: the
+// kernels' xcd & 1, XCD-contiguous eighths from 32 tiles per plane (SMSM's 512^2 planes: +1.9 % over plane order,
+// same box; smaller planes in plane order, 256^2: +1.4 % over the eighths; profiles/r03/boxmdot/xcd/) unless the
+// caller's tuning flag noxcd_flag is set.
+struct TileGrid {
+  int64_t grid;
+  int xcd1;
+  size_t lds;
+};
+static TileGrid tile_grid(int32_t nx, int64_t P, int32_t nz, int32_t zt, bool sym, int noxcd_flag) {
+  const int64_t cpp = P / kChunk;
+  return {cpp * ((nz + zt - 1) / zt), cpp % 8 == 0 && cpp >= 32 && !(msk_tuning_flags & noxcd_flag),
+          window_lds(nx, sym)};
+}
+
 // MSPLIT_MARCH_CHUNK=0 turns the chunk-tile march off (msk_spmv_box_march, msk_march_chunk_fits)
 static int march_chunk_env() {
   static const int v = env_int("MSPLIT_MARCH_CHUNK", 1);
@@ -2705,18 +2625,16 @@ static int launch_march_chunk(int32_t nx, int32_t ny, int32_t nz, int halo, cons
   const int32_t zt = msk_march_z_override > 0
                          ? msk_march_z_override
                          : (int32_t)std::max<int64_t>(1, std::min<int64_t>(nz, (cpp * nz + 511) / 512));
-  const int64_t grid = cpp * ((nz + zt - 1) / zt);
-  if (grid > INT32_MAX || (int64_t)nx * ny * nz > INT32_MAX) return (int)hipErrorInvalidValue;
-  const int xcd = cpp % 8 == 0 && cpp >= 32 && !(msk_tuning_flags & MSK_TUNE_ELL_MARCH_NOXCD);
-  const bool nty = !(msk_tuning_flags & MSK_TUNE_ELL_TEMPORAL_Y);
-  const size_t lds = (size_t)(kChunk + 2 * nx + (rv && rvs < 0 ? 2 * (kChunk + nx) : 0)) * sizeof(double);
   const int form = rv_form(rv, rvs);
+  const TileGrid tg = tile_grid(nx, P, nz, zt, form == 2, MSK_TUNE_ELL_MARCH_NOXCD);
+  if (tg.grid > INT32_MAX || (int64_t)nx * ny * nz > INT32_MAX) return (int)hipErrorInvalidValue;
+  const bool nty = !(msk_tuning_flags & MSK_TUNE_ELL_TEMPORAL_Y);
   pick_mode(mode, [&](auto m) {
     pick<true, false>(nty, [&](auto nt) {
       pick<0, 1, 2>(form, [&](auto f) {
         k_box_march_chunk<decltype(m)::value, decltype(nt)::value, decltype(f)::value>
-            <<<dim3((unsigned)grid), dim3(kT), lds, s>>>(nx, P, nz, zt, xcd, halo, mask, dval, rv, rvs, x, b, y, sdev, vout,
-                                                         stop);
+            <<<dim3((unsigned)tg.grid), dim3(kT), tg.lds, s>>>(nx, P, nz, zt, tg.xcd1, halo, mask, dval, rv, rvs, x, b, y,
+                                                               sdev, vout, stop);
       });
     });
   });
@@ -2732,7 +2650,6 @@ extern "C" int msk_spmv_box_march(int32_t nx, int32_t ny, int32_t nz, int d2, co
     return (int)hipErrorInvalidValue;
   if (msk_march_lines_override == 4 && nx % kT) return (int)hipErrorInvalidValue;
   if (d2 && msk_march_lines_override == 4) return (int)hipErrorInvalidValue;
-  auto a16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
   const bool chunk_ok = march_chunk_ok(nx, ny, d2) && a16(x) && a16(y) &&
                         (mode != MSK_SPMV_RESID || a16(b)) && (mode != MSK_SPMV_SCALED || !vout || a16(vout));
   if (msk_march_lines_override == 16 && !chunk_ok) return (int)hipErrorInvalidValue;
@@ -2770,7 +2687,6 @@ extern "C" int msk_box_march_halo_fits(int32_t nx, int32_t ny, int32_t nz, int h
                                        const double* b, const double* y, int mode) {
   if (nx <= 0 || ny <= 0 || nz <= 0 || dv_flags_bad() || mode == MSK_SPMV_SCALED) return 0;
   const double* xo = x + ((halo & 1) ? (int64_t)nx * ny : 0);
-  auto a16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
   return march_chunk_ok(nx, ny, 0) && a16(xo) && a16(y) && (mode != MSK_SPMV_RESID || a16(b));
 }
 
@@ -2788,7 +2704,6 @@ extern "C" int msk_box_march_halo(int32_t nx, int32_t ny, int32_t nz, int halo, 
 extern "C" int msk_box_march_chunk_rv(int32_t nx, int32_t ny, int32_t nz, const uint8_t* mask, const double* rv,
                                       int64_t rvs, const double* x, const double* b, double* y, int mode,
                                       const double* sdev, double* vout, const int* stop, hipStream_t s) {
-  auto a16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
   if (nx <= 0 || ny <= 0 || nz <= 0 || dv_flags_bad() || !march_chunk_ok(nx, ny, 0) || !rv || (rvs > 0 && (rvs & 1)) ||
       (rvs > 0 && rvs < (int64_t)nx * ny * nz) || (rvs < 0 && nx > 1024) || !a16(rv) || !a16(x) || !a16(y) ||
       (mode == MSK_SPMV_RESID && !a16(b)) ||
@@ -2928,8 +2843,6 @@ extern "C" int msk_box_spmv_mdot_rv(int32_t nx, int64_t P, int64_t n, int d2, co
   if (n <= 0 || nchunks <= 0) return 0;
   if (nx < 2 || nx > 2048 || P < nx || nv < 1 || nv > MSK_MAX_GROUP || dv_flags_bad()) return (int)hipErrorInvalidValue;
   if (rv && (!y || d2 || P % kChunk || n % P || (nx & 1) || (rvs < 0 && nx > 1024))) return (int)hipErrorInvalidValue;
-  // the symmetric storage adds the x+1 / y+1 legs' windows (2 x (4096 + nx) doubles; nx <= 1024: <= 128 KiB in all)
-  const size_t lds = (size_t)(kChunk + 2 * nx + (rv && rvs < 0 ? 2 * (kChunk + nx) : 0)) * sizeof(double);
   const dim3 g((unsigned)nchunks), b(kT);
   const bool nty = !(msk_tuning_flags & MSK_TUNE_ELL_TEMPORAL_Y);
   if (!d2 && P % kChunk == 0 && n % P == 0 && (nx & 1) == 0 && (rv || !(msk_tuning_flags & MSK_TUNE_BOX_MDOT_FLAT))) {
@@ -2940,10 +2853,9 @@ extern "C" int msk_box_spmv_mdot_rv(int32_t nx, int64_t P, int64_t n, int d2, co
     // and for the STENCIL storage its z+1 leg) -- STENCIL step +1.9 %, SMSM block +0.3 %, 256^3 GMRES +0.1 % against
     // two (profiles/r05/stencil_sym2/zt/, profiles/r05/zt_dv/); one plane was -1.0 % (profiles/r03/wfree/fused_depth/)
     const int32_t zt = zenv > 0 ? zenv : 4;
-    const int64_t grid = (P / kChunk) * ((nz + zt - 1) / zt);
-    if (grid > INT32_MAX) return (int)hipErrorInvalidValue;
-    // XCD-contiguous eighths from 32 tiles per plane (SMSM's 512^2 planes: +1.9 % over plane order, same box);
-    // smaller planes in plane order (256^2: +1.4 % over the eighths; profiles/r03/boxmdot/xcd/)
+    const int form = rv_form(rv, rvs);
+    const TileGrid tg = tile_grid(nx, P, nz, zt, form == 2, MSK_TUNE_BOX_MDOT_NOXCD);
+    if (tg.grid > INT32_MAX) return (int)hipErrorInvalidValue;
     static const int rev = env_int("MSPLIT_BOXMDOT_REV", 0) ? 2 : 0;
     // MSPLIT_BOXMDOT_ALT=1: odd plane groups march down (k_box_spmv_mdot_march, xcd & 4), so the boundary planes
     // two groups both read are read at the same moment, the second time from the L2.  Measured (round 6,
@@ -2953,8 +2865,7 @@ extern "C" int msk_box_spmv_mdot_rv(int32_t nx, int64_t P, int64_t n, int d2, co
     // other and to the oracle).  Its test is the first character, not env_int's number.
     const char* alte = getenv("MSPLIT_BOXMDOT_ALT");
     const int alt = alte && alte[0] == '1' ? 4 : 0;
-    const int xcd =
-        ((P / kChunk) % 8 == 0 && P / kChunk >= 32 && !(msk_tuning_flags & MSK_TUNE_BOX_MDOT_NOXCD)) | rev | alt;
+    const int xcd = tg.xcd1 | rev | alt;
     // GMRES's basis ends with x (VV(it)): its dot from the march registers (MSPLIT_BOXMDOT_SELF=0: streamed, A/B)
     static const int self_env = env_int("MSPLIT_BOXMDOT_SELF", 1);
     const double* last = V->base ? V->base + (int64_t)(nv - 1) * V->stride : V->p[nv - 1];
@@ -2968,26 +2879,24 @@ extern "C" int msk_box_spmv_mdot_rv(int32_t nx, int64_t P, int64_t n, int d2, co
     // read per call: the tests hold the two forms to each other; its test is the first character, not env_int's number
     const char* s2e = getenv("MSPLIT_RV_SYM2");
     const bool sym2 = !(s2e && s2e[0] == '0') && nx <= 512;
-    const int form = rv_form(rv, rvs);
     pick<1, 0>(vec_var(), [&](auto var) {
       pick<true, false>(nty, [&](auto nt) {
         constexpr int VAR = decltype(var)::value;
         constexpr bool NT = decltype(nt)::value;
         if (form == 2 && sym2) {
-          k_box_spmv_mdot_march_sym2<VAR, NT><<<dim3((unsigned)grid), dim3(2 * kT), lds, s>>>(
+          k_box_spmv_mdot_march_sym2<VAR, NT><<<dim3((unsigned)tg.grid), dim3(2 * kT), tg.lds, s>>>(
               nx, P, nz, zt, xcd, mask, rv, x, sdev, y, *V, nv, self, partial, nchunks, stop);
           return;
         }
         pick<0, 1, 2>(form, [&](auto f) {
           constexpr int RV = decltype(f)::value;
           auto go = [&](auto p) {
-            k_box_spmv_mdot_march<VAR, NT, RV, decltype(p)::value><<<dim3((unsigned)grid), b, lds, s>>>(
+            k_box_spmv_mdot_march<VAR, NT, RV, decltype(p)::value><<<dim3((unsigned)tg.grid), b, tg.lds, s>>>(
                 nx, P, nz, zt, xcd, mask, dval, rv, rvs, x, sdev, y, *V, nv, self, partial, nchunks, stop);
           };
-          // only the rows' own values (RV == 1) take the shorter prefetches.  The test is a run-time one, as it always
-          // was, so the library goes on holding the P = 4 and P = 2 kernels of the other two forms, which nothing
-          // launches (profiles/launch_dispatch/README.md); retiring them is a change of its own.
-          pick<kIters, 4, 2>(RV == 1 ? rvp : kIters, go);
+          // only the rows' own values (RV == 1) take the shorter prefetches
+          if constexpr (RV == 1) pick<kIters, 4, 2>(rvp, go);
+          else go(std::integral_constant<int, kIters>{});
         });
       });
     });
@@ -2996,7 +2905,7 @@ extern "C" int msk_box_spmv_mdot_rv(int32_t nx, int64_t P, int64_t n, int d2, co
   pick<true, false>(d2 != 0, [&](auto d) {
     pick<1, 0>(vec_var(), [&](auto var) {
       pick<true, false>(nty, [&](auto nt) {
-        k_box_spmv_mdot<decltype(d)::value, decltype(var)::value, decltype(nt)::value><<<g, b, lds, s>>>(
+        k_box_spmv_mdot<decltype(d)::value, decltype(var)::value, decltype(nt)::value><<<g, b, window_lds(nx, false), s>>>(
             nx, P, n, mask, dval, x, sdev, y, *V, nv, partial, nchunks, stop);
       });
     });
@@ -3028,12 +2937,12 @@ extern "C" int msk_box_maxpy_march(int32_t nx, int64_t P, int64_t n, int d2, con
   if (!box_mdot_marches(nx, P, n, d2)) {  // the unmarched form, one chunk per workgroup (as k_box_spmv_mdot)
     const int64_t nch = (n + kChunk - 1) / kChunk;
     if (nch > INT32_MAX) return (int)hipErrorInvalidValue;
-    const size_t ldsu = (size_t)(kChunk + 2 * nx) * sizeof(double);
     pick<true, false>(d2 != 0, [&](auto d) {
       pick<1, 0>(vec_var(), [&](auto var) {
         pick<true, false>(nt, [&](auto ntc) {
           k_box_maxpy<decltype(d)::value, decltype(var)::value, decltype(ntc)::value>
-              <<<dim3((unsigned)nch), dim3(kT), ldsu, s>>>(nx, P, n, mask, dval, x, sdev, wout, *V, nv, adev, partial, stop);
+              <<<dim3((unsigned)nch), dim3(kT), window_lds(nx, false), s>>>(nx, P, n, mask, dval, x, sdev, wout, *V, nv,
+                                                                           adev, partial, stop);
         });
       });
     });
@@ -3044,11 +2953,10 @@ extern "C" int msk_box_maxpy_march(int32_t nx, int64_t P, int64_t n, int d2, con
   // one plane per workgroup (x(z-+1) loaded per plane, twice the workgroups of the fused kernel's 2-plane march):
   // 256^3 GMRES step 2.261 -> 2.336e10 over 2 planes, MAXPY 392 -> 368 us (profiles/r03/wfree/ab/)
   const int32_t zt = zenv > 0 ? zenv : 1;
-  const int64_t grid = (P / kChunk) * ((nz + zt - 1) / zt);
-  if (grid > INT32_MAX) return (int)hipErrorInvalidValue;
+  const TileGrid tg = tile_grid(nx, P, nz, zt, false, MSK_TUNE_BOX_MDOT_NOXCD);
+  if (tg.grid > INT32_MAX) return (int)hipErrorInvalidValue;
   const int rev = maxpy_rev(n) ? 2 : 0;  // msk_maxpy_chunk's order
-  const int xcd = ((P / kChunk) % 8 == 0 && P / kChunk >= 32 && !(msk_tuning_flags & MSK_TUNE_BOX_MDOT_NOXCD)) | rev;
-  const size_t lds = (size_t)(kChunk + 2 * nx) * sizeof(double);
+  const int xcd = tg.xcd1 | rev;
   // MSPLIT_MAXPY_MARCH_U2=1: the group loop unrolled by two (A/B)
   static const int u2 = env_int("MSPLIT_MAXPY_MARCH_U2", 0);
   // the one-plane form where one plane per workgroup runs (MSPLIT_MAXPY_ZT > 1 keeps the marched form)
@@ -3064,7 +2972,8 @@ extern "C" int msk_box_maxpy_march(int32_t nx, int64_t P, int64_t n, int d2, con
   const int form = pf == 3 ? 2 : pf == 2 ? 1 : 0;  // the kernel's PF: 0 marched, 1 one plane, 2 its 8-vector burst
   auto go = [&](auto var, auto ntc, auto f) {
     k_box_maxpy_march<decltype(var)::value, decltype(ntc)::value, decltype(f)::value>
-        <<<dim3((unsigned)grid), dim3(kT), lds, s>>>(nx, P, nz, zt, xcd, mask, dval, x, sdev, wout, *V, nv, adev, partial, stop);
+        <<<dim3((unsigned)tg.grid), dim3(kT), tg.lds, s>>>(nx, P, nz, zt, xcd, mask, dval, x, sdev, wout, *V, nv, adev, partial,
+                                                          stop);
   };
   if (form == 0 && u2 && vec_var() && nt)  // the unrolled loop exists for the marched form with both policies on only
     go(std::integral_constant<int, 33>{}, std::true_type{}, std::integral_constant<int, 0>{});
