@@ -231,10 +231,31 @@ static int ksp_from_options(msp_ksp *k, const msd_options *o, const char *p, msp
   const char *kt = msd_opt_str(o, p, "ksp_type", "gmres"), *pt = msd_opt_str(o, p, "pc_type", "none");
   const int jacobi = !strcasecmp(pt, "jacobi");
   if (strcasecmp(kt, "gmres") || (strcasecmp(pt, "none") && !jacobi)) {
-    fprintf(stderr, "-%sksp_type %s -%spc_type %s: the MI355X path is gmres with pc none or jacobi\n", p, kt, p, pt);
+    fprintf(stderr, "-%sksp_type %s -%spc_type %s: the MI355X path is gmres with pc none or jacobi "
+                    "(conjugate gradients: -%smsplit_ksp_type cg)\n", p, kt, p, pt, p);
     return MSP_ERR_SUP;
   }
-  if (jacobi) {
+  /* -<prefix>msplit_ksp_type gmres|cg: the library's own key for the Krylov method (msp_ksp_set_type); under cg
+   * -<prefix>ksp_norm_type preconditioned|unpreconditioned is read, also with Jacobi */
+  const char *mt = msd_opt_str(o, p, "msplit_ksp_type", "gmres");
+  const int cg = !strcasecmp(mt, "cg");
+  if (!cg && strcasecmp(mt, "gmres")) {
+    fprintf(stderr, "-%smsplit_ksp_type %s: expected gmres or cg\n", p, mt);
+    return MSP_ERR_ARG_OUTOFRANGE;
+  }
+  if (cg) {
+    const char *side = msd_opt_str(o, p, "ksp_pc_side", "left"), *nt = msd_opt_str(o, p, "ksp_norm_type", "preconditioned");
+    const int unpre = !strcasecmp(nt, "unpreconditioned");
+    if (strcasecmp(side, "left") || (!unpre && strcasecmp(nt, "preconditioned")) ||
+        strcasecmp(msd_opt_str(o, p, "pc_jacobi_type", "diagonal"), "diagonal") || opt_bool(o, p, "pc_jacobi_abs", 0)) {
+      fprintf(stderr, "-%smsplit_ksp_type cg: only -%sksp_pc_side left, -%sksp_norm_type preconditioned or "
+                      "unpreconditioned and -%spc_jacobi_type diagonal without -%spc_jacobi_abs are implemented\n",
+              p, p, p, p, p);
+      return MSP_ERR_SUP;
+    }
+    CK(msp_ksp_set_type(k, MSP_KSP_CG));
+    CK(msp_ksp_set_norm_type(k, unpre ? MSP_NORM_UNPRECONDITIONED : MSP_NORM_PRECONDITIONED));
+  } else if (jacobi) {
     /* left Jacobi with the preconditioned norm (KSPGMRES's defaults) is what is built; nothing else of PCJACOBI */
     const char *side = msd_opt_str(o, p, "ksp_pc_side", "left"), *nt = msd_opt_str(o, p, "ksp_norm_type", "preconditioned");
     const char *jt = msd_opt_str(o, p, "pc_jacobi_type", "diagonal");
@@ -363,6 +384,13 @@ static int block_init(msp_ctx *ctx, const msd_problem *p, const msd_options *o, 
   CK(msp_ksp_create(ctx, &B->ksp));
   CK(msp_ksp_set_operators(B->ksp, B->A));
   CK(ksp_from_options(B->ksp, o, prefix, &B->ko));
+  int kt = MSP_KSP_GMRES;
+  CK(msp_ksp_get_type(B->ksp, &kt));
+  if (kt == MSP_KSP_CG && (L->peclet[0] != 0.0 || L->peclet[1] != 0.0 || L->peclet[2] != 0.0)) {
+    fprintf(stderr, "-%smsplit_ksp_type cg with a non-zero -peclet: the convection-diffusion operator is not symmetric\n",
+            prefix);
+    return MSP_ERR_SUP;
+  }
   return MSP_SUCCESS;
 }
 

@@ -53,7 +53,9 @@ extern "C" {
 #define MSP_DIVERGED_ITS (-3)
 #define MSP_DIVERGED_DTOL (-4)
 #define MSP_DIVERGED_BREAKDOWN (-5)
+#define MSP_DIVERGED_INDEFINITE_PC (-8)
 #define MSP_DIVERGED_NANORINF (-9)
+#define MSP_DIVERGED_INDEFINITE_MAT (-10)
 
 /* Kernel classes for msp_ctx_get_kernel_stats(). */
 #define MSP_KERNEL_SPMV 0       /* MatMult / MatResidual (CSR) */
@@ -363,7 +365,7 @@ int msp_ksp_set_basis_precision(msp_ksp *ksp, int prec);
 int msp_ksp_get_basis_precision(const msp_ksp *ksp, int *prec);
 /* Device bytes the KSP holds once set up and solved with: the basis, W / the current vector, the recurrence
  * block (with the CGS refinement's block behind it), and under MSP_PC_JACOBI the n doubles of the inverse diagonal
- * (0 before set-up). */
+ * (0 before set-up).  Under MSP_KSP_CG: r, w and p, the state block with the history, and dinv under Jacobi. */
 int msp_ksp_get_work_bytes(const msp_ksp *ksp, int64_t *bytes);
 /* Preconditioner (-pc_type none|jacobi).
  * MSP_PC_NONE (default): PCNONE.
@@ -387,6 +389,38 @@ int msp_ksp_get_work_bytes(const msp_ksp *ksp, int64_t *bytes);
 #define MSP_PC_JACOBI 1
 int msp_ksp_set_pc_type(msp_ksp *ksp, int pc_type);
 int msp_ksp_get_pc_type(const msp_ksp *ksp, int *pc_type);
+/* Krylov method (-msplit_ksp_type gmres|cg).
+ * MSP_KSP_GMRES (default): KSPGMRES; nothing changes, bit for bit.
+ * MSP_KSP_CG: PETSc's KSPCG for symmetric positive definite operators: KSP_CG_SYMMETRIC, MSP_PC_NONE or left
+ * MSP_PC_JACOBI, the norm taken every iteration.  One MatMult, two reductions and three vector updates per
+ * iteration; the work is three n-vectors (r, w, p) and the state block, whatever max_it is.
+ *   start    x = 0 and r = b, or r = b - A x (MatResidual) for a nonzero guess; z = dinv .* r (PCNONE: z is r);
+ *            dp = ||z|| (MSP_NORM_PRECONDITIONED) or ||r|| (MSP_NORM_UNPRECONDITIONED); history[0] = dp;
+ *            KSPConvergedDefault(0, dp) as for GMRES (rnorm0, uirnorm, ||b|| resp. ||dinv .* b|| for a nonzero
+ *            guess, NaN / inf: MSP_DIVERGED_NANORINF, rtol / abstol / divtol); beta = z . r.
+ *   step i   its = i + 1.  beta == 0: MSP_CONVERGED_ATOL.  i > 0 and beta betaold < 0: MSP_DIVERGED_INDEFINITE_PC.
+ *            p = z (i = 0), else p = z + (beta / betaold) p (VecAYPX).  w = A p, dpi = p . w.  dpi not finite:
+ *            MSP_DIVERGED_NANORINF.  dpi == 0, or i > 0 and dpi changed sign: MSP_DIVERGED_INDEFINITE_MAT.
+ *            a = beta / dpi; x = x + a p; r = r + (-a) w (two VecAXPY); z, dp, history[i + 1] = dp and
+ *            KSPConvergedDefault(i + 1, dp) as at the start; beta = z . r (not finite: MSP_DIVERGED_NANORINF).
+ *   end      max_it iterations without a reason: MSP_DIVERGED_ITS (max_it = 0: its 0).
+ *   Every sum is a DBR sum, every element operation rounds once.  z is never stored.  restart, haptol and
+ *   breakdowntol of msp_ksp_opts are ignored.
+ * A solve under MSP_KSP_CG returns MSP_ERR_SUP, naming the cause, with MSP_BASIS_F32 / MSP_BASIS_B16, with
+ * MSP_OPER_F32, with a CGS refinement other than MSP_CGS_REFINE_NEVER, and on a context in MSP_REDUCE_SEQ.  An
+ * operator that is not symmetric positive definite is not refused: the solve ends with one of the reasons above
+ * or does not converge.  Changing the type frees the work of an earlier set-up and drops the captured cycles.
+ * Any other value: MSP_ERR_ARG_OUTOFRANGE.
+ * The norm type (-ksp_norm_type preconditioned|unpreconditioned) is read by MSP_KSP_CG only; with MSP_PC_NONE
+ * the two are the same norm.  KSP_NORM_NATURAL is not implemented.  Any other value: MSP_ERR_ARG_OUTOFRANGE. */
+#define MSP_KSP_GMRES 0
+#define MSP_KSP_CG 1
+int msp_ksp_set_type(msp_ksp *ksp, int type);        /* KSPSetType */
+int msp_ksp_get_type(const msp_ksp *ksp, int *type); /* KSPGetType */
+#define MSP_NORM_PRECONDITIONED 0
+#define MSP_NORM_UNPRECONDITIONED 1
+int msp_ksp_set_norm_type(msp_ksp *ksp, int norm);        /* KSPSetNormType */
+int msp_ksp_get_norm_type(const msp_ksp *ksp, int *norm); /* KSPGetNormType */
 /* Storage precision of the operator's values in the Arnoldi products (-msplit_operator_precision double|single).
  * MSP_OPER_F64 (default): every product reads the operator as it is stored; nothing changes.
  * MSP_OPER_F32: compressed-operator GMRES for an operator whose products read its CSR arrays (MSP_STORAGE_CSR).

@@ -23,7 +23,8 @@ REASONS = {
     0: "CONVERGED_ITERATING", 1: "CONVERGED_RTOL_NORMAL", 2: "CONVERGED_RTOL", 3: "CONVERGED_ATOL",
     4: "CONVERGED_ITS", 9: "CONVERGED_ATOL_NORMAL",
     -2: "DIVERGED_NULL", -3: "DIVERGED_ITS", -4: "DIVERGED_DTOL",
-    -5: "DIVERGED_BREAKDOWN", -9: "DIVERGED_NANORINF",
+    -5: "DIVERGED_BREAKDOWN", -8: "DIVERGED_INDEFINITE_PC", -9: "DIVERGED_NANORINF",
+    -10: "DIVERGED_INDEFINITE_MAT",
 }
 
 
@@ -113,6 +114,10 @@ _SIGS = {
     "msp_ksp_set_pc_type": [_vp, C.c_int],
     "msp_ksp_get_pc_type": [_vp, _P(C.c_int)],
     "msp_mat_get_diagonal": [_vp, _vp],
+    "msp_ksp_set_type": [_vp, C.c_int],
+    "msp_ksp_get_type": [_vp, _P(C.c_int)],
+    "msp_ksp_set_norm_type": [_vp, C.c_int],
+    "msp_ksp_get_norm_type": [_vp, _P(C.c_int)],
     "msp_ksp_set_operator_precision": [_vp, C.c_int],
     "msp_ksp_get_operator_precision": [_vp, _P(C.c_int)],
     "msp_ksp_set_cgs_refinement": [_vp, C.c_int],

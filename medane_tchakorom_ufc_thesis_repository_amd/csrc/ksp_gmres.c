@@ -7,6 +7,10 @@
  * KSPConvergedDefault with PCNONE -- the inner solve the reference calls from
  * inner_solver() (src/utils/utils.c:950-970) and gmres_solution.c:70.
  *
+ * This file also holds what both KSP types share (struct msp_ksp is in ksp_impl.h): creation, options, the
+ * preconditioner's set-up, the graph cache and the result getters; msp_ksp_set_up and msp_ksp_solve hand a KSP of
+ * type MSP_KSP_CG to ksp_cg.c.
+ *
  * Division of labour.  This file owns the solve: options, the restart loop of
  * KSPSolve_GMRES, the order of every operation, and the decision to start
  * another cycle.  The per-iteration scalar steps of KSPGMRESCycle (Givens
@@ -83,52 +87,7 @@
 
 #include "msplit.h"
 #include "msplit_internal.h"
-
-/* Captured restart cycles (HIP graphs), keyed by everything the capture baked
- * in: the operator and the kernels its products launch, the context's DBR
- * partial buffer (its epoch), x, the cycle length K, the tuning flags and the launch-shape overrides.  The basis, W and the device state are fixed
- * between ksp_free_work calls, which drop the cache. */
-#define KSP_NGRAPH 4
-typedef struct {
-  void *exec;
-  const msp_mat *A;
-  uint64_t aver, epoch;
-  const double *x;
-  int K, tuning, shape;
-} ksp_graph;
-
-struct msp_ksp {
-  msp_ctx *ctx;
-  ksp_graph graphs[KSP_NGRAPH];
-  int gnext;
-  int graphs_off; /* a capture failed on this KSP's stream (e.g. the legacy null stream): eager from then on */
-  msp_mat *A;
-  msp_ksp_opts o;
-  int setup;
-  int64_t n, stride;
-  int basis_prec;           /* MSP_BASIS_F64 / MSP_BASIS_F32 / MSP_BASIS_B16: the element type behind basis */
-  double *basis;            /* device: (m+1) * stride, stored unnormalised (scales in g.sc); floats when F32, int16
-                               followed by the exponent table when B16 */
-  int32_t *expo;            /* device, B16 only: exponents [vector][nchunks], inside the basis allocation */
-  int64_t nchunks;          /* DBR chunks per vector */
-  double *tmp;              /* device: W = A VV(it) before the orthogonalisation */
-  double *cur;              /* device, F32 / B16: the newest basis vector's rounded values as doubles */
-  int pc_type;              /* MSP_PC_NONE / MSP_PC_JACOBI */
-  double *dinv;             /* device, Jacobi: n doubles, 1 / a_ii by PCSetUp's rule */
-  int dinv_valid;           /* dinv holds the current operator's (reset by msp_ksp_set_operators) */
-  int oper_prec;            /* MSP_OPER_F64 / MSP_OPER_F32: what the Arnoldi MatMult reads */
-  int cgs;                  /* MSP_CGS_REFINE_NEVER / _IFNEEDED / _ALWAYS */
-  mspi_gmres_refine *rf;    /* device: the refinement's block, behind the recurrence arrays in gblock */
-  int nrefine;              /* steps of the last solve that ran pass 2 */
-  size_t basis_bytes, gblock_bytes, vec_bytes; /* sizes of the allocations (vec_bytes: tmp and cur, each) */
-  mspi_gmres_dev g;         /* device-resident recurrence state and arrays */
-  void *gblock;             /* the single device allocation behind g */
-  mspi_gmres_state *hst;    /* pinned host mirror of *g.st */
-  double *hist;             /* host copy of the residual history */
-  int hist_cap, nhist;
-  int its, reason;
-  double rnorm;
-};
+#include "ksp_impl.h"
 
 int msp_ksp_get_default_opts(msp_ksp_opts *o) {
   if (!o) {
@@ -160,11 +119,12 @@ int msp_ksp_create(msp_ctx *ctx, msp_ksp **out) {
   k->ctx = ctx;
   mspi_ctx_retain(ctx);
   msp_ksp_get_default_opts(&k->o);
+  k->cg_route_set = MSPI_CG_ROUTE_AUTO;
   *out = k;
   return MSP_SUCCESS;
 }
 
-static void ksp_drop_graphs(msp_ksp *k) {
+void ksp_drop_graphs(msp_ksp *k) {
   for (int i = 0; i < KSP_NGRAPH; ++i) {
     mspi_graph_destroy(k->graphs[i].exec);
     memset(&k->graphs[i], 0, sizeof(k->graphs[i]));
@@ -172,7 +132,7 @@ static void ksp_drop_graphs(msp_ksp *k) {
   k->gnext = 0;
 }
 
-static void ksp_free_work(msp_ksp *k) {
+void ksp_free_work(msp_ksp *k) {
   ksp_drop_graphs(k);
   if (k->basis) mspi_free(k->ctx, k->basis);
   if (k->tmp) mspi_free(k->ctx, k->tmp);
@@ -180,6 +140,13 @@ static void ksp_free_work(msp_ksp *k) {
   if (k->dinv) mspi_free(k->ctx, k->dinv);
   if (k->gblock) mspi_free(k->ctx, k->gblock);
   if (k->hst) mspi_host_free(k->hst);
+  if (k->cg_r) mspi_free(k->ctx, k->cg_r);
+  if (k->cg_w) mspi_free(k->ctx, k->cg_w);
+  if (k->cg_p) mspi_free(k->ctx, k->cg_p);
+  if (k->cg_p2) mspi_free(k->ctx, k->cg_p2);
+  if (k->cg_hst) mspi_host_free(k->cg_hst);
+  k->cg_r = k->cg_w = k->cg_p = k->cg_p2 = k->cg_hist = NULL;
+  k->cg_st = k->cg_hst = NULL;
   free(k->hist);
   k->basis = k->tmp = k->cur = k->dinv = NULL;
   k->dinv_valid = 0;
@@ -304,6 +271,59 @@ int msp_ksp_get_pc_type(const msp_ksp *k, int *pc_type) {
   return MSP_SUCCESS;
 }
 
+int msp_ksp_set_type(msp_ksp *k, int type) {
+  if (!k) {
+    mspi_set_error(MSP_ERR_ARG_NULL, "NULL argument");
+    return MSP_ERR_ARG_NULL;
+  }
+  if (type != MSP_KSP_GMRES && type != MSP_KSP_CG) {
+    mspi_set_error(MSP_ERR_ARG_OUTOFRANGE, "KSP type %d is neither MSP_KSP_GMRES nor MSP_KSP_CG", type);
+    return MSP_ERR_ARG_OUTOFRANGE;
+  }
+  if (type != k->type) { /* other work vectors and another state block: no graph survives */
+    msp_ctx_synchronize(k->ctx);
+    ksp_free_work(k);
+  }
+  k->type = type;
+  return MSP_SUCCESS;
+}
+
+int msp_ksp_get_type(const msp_ksp *k, int *type) {
+  if (!k || !type) {
+    mspi_set_error(MSP_ERR_ARG_NULL, "NULL argument");
+    return MSP_ERR_ARG_NULL;
+  }
+  *type = k->type;
+  return MSP_SUCCESS;
+}
+
+int msp_ksp_set_norm_type(msp_ksp *k, int norm) {
+  if (!k) {
+    mspi_set_error(MSP_ERR_ARG_NULL, "NULL argument");
+    return MSP_ERR_ARG_NULL;
+  }
+  if (norm != MSP_NORM_PRECONDITIONED && norm != MSP_NORM_UNPRECONDITIONED) {
+    mspi_set_error(MSP_ERR_ARG_OUTOFRANGE,
+                   "norm type %d is neither MSP_NORM_PRECONDITIONED nor MSP_NORM_UNPRECONDITIONED", norm);
+    return MSP_ERR_ARG_OUTOFRANGE;
+  }
+  if (norm != k->norm_type) { /* another kernel in every captured CG cycle; the work vectors stay */
+    msp_ctx_synchronize(k->ctx);
+    ksp_drop_graphs(k);
+  }
+  k->norm_type = norm;
+  return MSP_SUCCESS;
+}
+
+int msp_ksp_get_norm_type(const msp_ksp *k, int *norm) {
+  if (!k || !norm) {
+    mspi_set_error(MSP_ERR_ARG_NULL, "NULL argument");
+    return MSP_ERR_ARG_NULL;
+  }
+  *norm = k->norm_type;
+  return MSP_SUCCESS;
+}
+
 int msp_ksp_set_operator_precision(msp_ksp *k, int prec) {
   if (!k) {
     mspi_set_error(MSP_ERR_ARG_NULL, "NULL argument");
@@ -373,12 +393,13 @@ int msp_ksp_get_work_bytes(const msp_ksp *k, int64_t *bytes) {
     return MSP_ERR_ARG_NULL;
   }
   *bytes = (int64_t)(k->basis_bytes + k->gblock_bytes + (k->tmp ? k->vec_bytes : 0) + (k->cur ? k->vec_bytes : 0) +
+                    (k->cg_r ? 3 * k->vec_bytes : 0) + (k->cg_p2 ? k->vec_bytes : 0) +
                     (k->dinv ? (size_t)k->n * sizeof(double) : 0));
   return MSP_SUCCESS;
 }
 
 /* PCSetUp of MSP_PC_JACOBI: dinv allocated with the work, computed once per operator */
-static int pc_set_up(msp_ksp *k) {
+int ksp_pc_set_up(msp_ksp *k) {
   if (k->pc_type != MSP_PC_JACOBI || k->dinv_valid) return MSP_SUCCESS;
   int rc = MSP_SUCCESS;
   if (!k->dinv) rc = mspi_malloc(k->ctx, (void **)&k->dinv, (size_t)(k->n ? k->n : 1) * sizeof(double));
@@ -392,7 +413,8 @@ int msp_ksp_set_up(msp_ksp *k) {
     mspi_set_error(MSP_ERR_ARG_WRONG, "KSPSetUp before KSPSetOperators");
     return MSP_ERR_ARG_WRONG;
   }
-  if (k->setup) return pc_set_up(k);
+  if (k->type == MSP_KSP_CG) return ksp_cg_set_up(k);
+  if (k->setup) return ksp_pc_set_up(k);
   const int64_t m = k->o.restart;
   /* a cycle runs K <= min(restart, max_it) steps and touches VV(0..K): with max_it < restart (the campaign's
    * inner solves, max_it 20 under GMRES(30)) only max_it + 1 basis vectors are ever used -- 11 of 32 GB less
@@ -446,7 +468,7 @@ int msp_ksp_set_up(msp_ksp *k) {
   k->g.hist = d;
   k->rf = (mspi_gmres_refine *)(d + k->hist_cap);
   k->setup = 1;
-  if ((rc = pc_set_up(k))) ksp_free_work(k);
+  if ((rc = ksp_pc_set_up(k))) ksp_free_work(k);
   return rc;
 }
 
@@ -625,7 +647,7 @@ static int enqueue_cycle(msp_ksp *k, double *x, int K) {
  * replayed with one hipGraphLaunch (the host enqueues ~5 launches per Arnoldi
  * step otherwise, which small systems feel).  Same kernels, same arguments,
  * same order: results are those of the eager enqueue. */
-static int run_cycle(msp_ksp *k, double *x, int K) {
+int ksp_run_cycle(msp_ksp *k, double *x, int K, int (*enqueue_cycle)(msp_ksp *, double *, int)) {
   msp_ctx *c = k->ctx;
   if (k->graphs_off || !mspi_graphs_enabled(c)) return enqueue_cycle(k, x, K);
   int rc = mspi_reserve_partial(c, k->n); /* before the lookup: it may reallocate (a new epoch) */
@@ -637,7 +659,7 @@ static int run_cycle(msp_ksp *k, double *x, int K) {
   for (int i = 0; i < KSP_NGRAPH; ++i) {
     const ksp_graph *g = &k->graphs[i];
     if (g->exec && g->A == k->A && g->aver == aver && g->epoch == epoch && g->x == x && g->K == K &&
-        g->tuning == tuning && g->shape == shape)
+        g->tuning == tuning && g->shape == shape && g->type == k->type)
       return mspi_graph_launch(c, g->exec);
   }
   if (mspi_capture_begin(c)) { /* stream cannot be captured: run it eagerly */
@@ -663,6 +685,7 @@ static int run_cycle(msp_ksp *k, double *x, int K) {
   g->K = K;
   g->tuning = tuning;
   g->shape = shape;
+  g->type = k->type;
   return mspi_graph_launch(c, exec);
 }
 
@@ -684,6 +707,7 @@ int msp_ksp_solve(msp_ksp *k, const msp_vec *b, msp_vec *x) {
     mspi_set_error(MSP_ERR_ARG_WRONG, "b and x must be different vectors");
     return MSP_ERR_ARG_WRONG;
   }
+  if (k->type == MSP_KSP_CG) return ksp_cg_solve(k, b, x);
   if (compressed(k) && mspi_reduce_seq(k->ctx)) {
     mspi_set_error(MSP_ERR_SUP, "%s needs the DBR reduction: MSP_REDUCE_SEQ reproduces PETSc's f64 "
                                 "sums bit for bit, which a rounded basis cannot",
@@ -774,7 +798,7 @@ int msp_ksp_solve(msp_ksp *k, const msp_vec *b, msp_vec *x) {
     int K = k->o.max_it - its;
     if (K > k->o.restart) K = k->o.restart;
     if (K < 0) K = 0;
-    if ((rc = run_cycle(k, x->d, K))) return rc;
+    if ((rc = ksp_run_cycle(k, x->d, K, enqueue_cycle))) return rc;
     if ((rc = mspi_d2h_sync(c, h, k->g.st, sizeof(*h)))) return rc; /* the one sync per cycle */
     its = h->its;
     reason = h->reason;

@@ -348,6 +348,61 @@ typedef struct {
   double *hist;         /* hist_cap */
 } mspi_lsqr_dev;
 
+/* ---- device-resident KSPCG state and step launchers (msplit_k_cg.hip, driven by ksp_cg.c) ---- */
+typedef struct {
+  int32_t stop;        /* solve over: later kernels return at once */
+  int32_t reason;      /* KSPConvergedReason */
+  int32_t its;         /* ksp->its */
+  int32_t i;           /* loop counter of KSPSolve_CG: the iteration the next launches run */
+  int32_t nhist;       /* residual history entries written */
+  int32_t max_it, hist_cap;
+  int32_t guess_zero, uirnorm;
+  int32_t jacobi;      /* two sums per sweep: row 0 = z . r, row 1 = ||z||^2 or ||r||^2 */
+  int32_t pad[2];
+  double one;          /* 1.0: the scale the fused MatMult + dot multiplies by */
+  double a, na;        /* beta / dpi and its negation (VecAXPY's two scalars) */
+  double b;            /* beta / betaold (VecAYPX's scalar) */
+  double pw;           /* p . w as the dot's stage 2 left it; mspi_cg_pw moves it into dpi */
+  double beta, betaold, dpi, dpiold;
+  double dp, rnorm, rnorm0, ttol;
+  double bnorm;        /* ||b|| resp. ||dinv .* b|| for KSPConvergedDefault(0) with a nonzero guess and no UIRNorm */
+  double rtol, abstol, divtol;
+} mspi_cg_state;
+
+/* Every launcher below honours st->stop (no store), writes its outputs and nothing else, and neither sums nor
+   writes beyond n.  DBR reduction only.  dinv == NULL: PCNONE (z is r). */
+/* p = z + st->b p with z = dinv .* r formed in registers; p = z when st->i == 0 */
+int mspi_cg_aypx(msp_ctx *ctx, const double *r, const double *dinv, double *p, int64_t n, const mspi_cg_state *st);
+/* The routes of an iteration's p, w = A p and p . w; all give the same bits.  mspi_cg_best_route: the one a solve
+   takes by default, asked once per solve (nothing is probed inside the cycle): FUSED where A takes it, else TWO.
+   MARCH measured slower than FUSED and is taken only when mspi_ksp_cg_set_route forces it. */
+#define MSPI_CG_ROUTE_AUTO (-1)
+#define MSPI_CG_ROUTE_TWO 0   /* mspi_cg_aypx, MatMult, dot */
+#define MSPI_CG_ROUTE_FUSED 1 /* mspi_cg_aypx, the operator's fused MatMult + self-dot (mspi_spmv_mdot_takes) */
+#define MSPI_CG_ROUTE_MARCH 2 /* mspi_cg_march: the AYPX folded into the chunk-tile march (mspi_cg_march_fits) */
+int mspi_spmv_mdot_takes(const msp_mat *A);
+int mspi_cg_march_fits(const msp_mat *A);
+int mspi_cg_best_route(const msp_mat *A);
+/* w = A p and st->pw = p . w (both DBR stages) by MSPI_CG_ROUTE_FUSED or MSPI_CG_ROUTE_TWO */
+int mspi_cg_matmult_dot(msp_mat *A, const double *p, double *w, mspi_cg_state *st, int route);
+/* pnew = z + st->b pold (pnew = z at st->i == 0, pold not read), w = A pnew, st->pw = pnew . w; pnew != pold */
+int mspi_cg_march(msp_mat *A, const double *r, const double *dinv, const double *pold, double *pnew, double *w,
+                  mspi_cg_state *st);
+/* Test and measurement hook: the route this KSP's CG solves take (MSPI_CG_ROUTE_AUTO, the default: the best one);
+   a route the operator does not take is MSP_ERR_SUP at solve.  Drops the captured cycles. */
+int mspi_ksp_cg_set_route(msp_ksp *ksp, int route);
+/* the scalar step after p . w: the sign tests, betaold, a (one lane) */
+int mspi_cg_pw(msp_ctx *ctx, mspi_cg_state *st);
+/* x += a p ; r += (-a) w ; stage-1 partials of z . r (row 0) and, under Jacobi, of ||z||^2 or ||r||^2 (row 1) */
+int mspi_cg_update(msp_ctx *ctx, double *x, const double *p, double *r, const double *w, const double *dinv,
+                   int norm_unpre, int64_t n, const mspi_cg_state *st);
+/* the same sums of the initial residual, nothing written but the partials; no stop flag */
+int mspi_cg_sums(msp_ctx *ctx, const double *r, const double *dinv, int norm_unpre, int64_t n);
+/* stage 2 of the initial sums, dp, hist[0], KSPConvergedDefault(0), beta and the tests of iteration 0 */
+int mspi_cg_start(msp_ctx *ctx, mspi_cg_state *st, double *hist, int64_t n);
+/* stage 2 of the sweep's sums, dp, history, KSPConvergedDefault(i + 1), beta, and the top of iteration i + 1 */
+int mspi_cg_iter_end(msp_ctx *ctx, mspi_cg_state *st, double *hist, int64_t n);
+
 /* ---- MSP_REDUCE_SEQ (msplit_seq.hip) ---- */
 int mspi_reduce_seq(const msp_ctx *ctx);
 #define MSPI_SEQ_MAXSEG 16

@@ -159,6 +159,13 @@ int msk_box_spmv_mdot_rv(int32_t nx, int64_t P, int64_t n, int d2, const uint8_t
 int msk_box_spmv_mdot(int32_t nx, int64_t P, int64_t n, int d2, const uint8_t* mask, const double* dval,
                       const double* x, const double* sdev, double* y, const Vecs* V, int nv, double* partial,
                       int64_t nchunks, const int* stop, int* self_out, hipStream_t s);
+// KSPCG on a DV box stencil whose planes hold whole DBR chunks (msk_box_cg_march_fits): pnew = z + bdev[0] pold with
+// z = dinv .* r (dinv null: r), pnew = z when iter[0] == 0 (pold not read); w = A pnew; partial[c] = the stage-1
+// partials of pnew . w -- k_cg_aypx then msk_box_spmv_mdot with one vector, bitwise.  pnew != pold.
+int msk_box_cg_march_fits(int32_t nx, int64_t P, int64_t n, int d2);
+int msk_box_cg_march(int32_t nx, int64_t P, int64_t n, int d2, const uint8_t* mask, const double* dval,
+                     const double* r, const double* dinv, const double* pold, const int* iter, const double* bdev,
+                     double* pnew, double* w, double* partial, int64_t nchunks, const int* stop, hipStream_t s);
 // The W-free GMRES step: msk_box_spmv_mdot with y = null (W not stored), then msk_box_maxpy_march, which
 // recomputes W for its rows on the same march tiles (bitwise) and runs the CGS VecMAXPY wout = W - sum_j adev_j
 // VV(j) with the DBR partials of ||wout||^2 (k_maxpy_chunk's arithmetic; V's last vector must be x).

@@ -1555,6 +1555,117 @@ __global__ __launch_bounds__(kT) void k_box_spmv_mdot_march(int32_t nx, int64_t 
   }
 }
 
+// KSPCG's VecAYPX folded into the march (DV box whose planes hold whole chunks): the tile forms
+// p_new = z + b p_old, z = dinv .* r (JAC) or r, for its rows, its window's halo lines and its neighbour planes as
+// it loads them -- so every x value of k_box_spmv_mdot_march is a p_new value here, recomputed from r and p_old
+// where another tile owns the row -- stores its own rows of p_new and of w = A p_new and leaves the stage-1
+// partials of p_new . w (the self dot of the march's registers).  p_new and p_old are different buffers, so no tile
+// reads a row another tile writes.  iter[0] == 0: p_new = z and p_old is not read.  Rows, terms and sums are
+// k_cg_aypx's followed by k_box_spmv_mdot_march's with scale 1.0 (x * 1.0 is exact), bit for bit.
+template <bool JAC>
+__device__ __forceinline__ double2 cg_p_pair(const double* __restrict__ r, const double* __restrict__ dinv,
+                                             const double* __restrict__ pold, bool first, double b, int64_t i,
+                                             bool has) {
+  if (!has) return make_double2(0.0, 0.0);
+  double2 z = *reinterpret_cast<const double2*>(r + i);
+  if constexpr (JAC) {
+    const double2 d = *reinterpret_cast<const double2*>(dinv + i);
+    z.x = z.x * d.x;
+    z.y = z.y * d.y;
+  }
+  if (first) return z;
+  const double2 p = *reinterpret_cast<const double2*>(pold + i);
+  return make_double2(z.x + b * p.x, z.y + b * p.y);
+}
+
+template <bool JAC, bool NTY>
+__global__ __launch_bounds__(kT) void k_box_cg_march(int32_t nx, int64_t P, int32_t nz, int32_t zt, int xcd,
+                                                     const uint8_t* __restrict__ mask,
+                                                     const double* __restrict__ dval, const double* __restrict__ r,
+                                                     const double* __restrict__ dinv,
+                                                     const double* __restrict__ pold, const int* __restrict__ iter,
+                                                     const double* __restrict__ bdev, double* __restrict__ pnew,
+                                                     double* __restrict__ w, double* __restrict__ partial,
+                                                     const int* __restrict__ stop) {
+  if (stopped(stop)) return;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  double* sx = reinterpret_cast<double*>(smem);  // window of plane z: kChunk + 2 nx doubles
+  __shared__ double red[4];
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const bool first = *iter == 0;
+  const double b = *bdev;
+  const int64_t cpp = P / kChunk, n = (int64_t)nz * P;
+  int64_t tile, zg;
+  tile_of<false>(cpp, nz, zt, xcd, tile, zg);
+  const int32_t z0 = (int32_t)zg * zt, z1 = min(z0 + zt, nz);
+  double v[7];
+  march_values<false>(dval, v);
+  double xm[2 * kIters], xc[2 * kIters], xp[2 * kIters];
+  {
+    const int64_t b0 = (int64_t)z0 * P + tile * kChunk + 2 * t;
+#pragma unroll
+    for (int j = 0; j < kIters; ++j) {
+      const double2 c2 = cg_p_pair<JAC>(r, dinv, pold, first, b, b0 + j * (2 * kT), true);
+      const double2 m2 = cg_p_pair<JAC>(r, dinv, pold, first, b, b0 - P + j * (2 * kT), z0 > 0);
+      xc[2 * j] = c2.x;
+      xc[2 * j + 1] = c2.y;
+      xm[2 * j] = m2.x;
+      xm[2 * j + 1] = m2.y;
+    }
+  }
+  for (int32_t z = z0; z < z1; ++z) {
+    const int64_t c = (int64_t)z * cpp + tile, c0 = c * kChunk, base = c0 + 2 * t;
+    const bool hasp = z + 1 < nz;
+    uint32_t m[kIters];
+#pragma unroll
+    for (int j = 0; j < kIters; ++j) {
+      const double2 p2 = cg_p_pair<JAC>(r, dinv, pold, first, b, base + P + j * (2 * kT), hasp);
+      xp[2 * j] = p2.x;
+      xp[2 * j + 1] = p2.y;
+      m[j] = mask_pair(mask + base + j * (2 * kT));
+    }
+    const bool inl = c0 - nx >= 0, inh = c0 + kChunk + nx <= n;
+    XWin xw;
+    xw.hl = cg_p_pair<JAC>(r, dinv, pold, first, b, c0 - nx + 2 * t, t < nx / 2 && inl);
+    xw.hh = cg_p_pair<JAC>(r, dinv, pold, first, b, c0 + kChunk + 2 * t, t < nx / 2 && inh);
+    __syncthreads();  // the previous plane's window reads (and its partial write) are done
+#pragma unroll
+    for (int j = 0; j < kIters; ++j)
+      *reinterpret_cast<double2*>(sx + nx + j * (2 * kT) + 2 * t) = make_double2(xc[2 * j], xc[2 * j + 1]);
+    if (t < nx / 2) {
+      *reinterpret_cast<double2*>(sx + 2 * t) = xw.hl;
+      *reinterpret_cast<double2*>(sx + nx + kChunk + 2 * t) = xw.hh;
+    }
+    for (int i = t + kT; i < nx / 2; i += kT) {  // nx > 512: the rest of the halo lines
+      *reinterpret_cast<double2*>(sx + 2 * i) = cg_p_pair<JAC>(r, dinv, pold, first, b, c0 - nx + 2 * i, inl);
+      *reinterpret_cast<double2*>(sx + nx + kChunk + 2 * i) =
+          cg_p_pair<JAC>(r, dinv, pold, first, b, c0 + kChunk + 2 * i, inh);
+    }
+    __syncthreads();
+    double acc = 0.0;
+#pragma unroll
+    for (int j = 0; j < kIters; ++j) {
+      double wr[2];
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        const int e = j * (2 * kT) + 2 * t + q + nx;
+        double xq[7];
+        window_x(sx, e, nx, xm[2 * j + q], xc[2 * j + q], xp[2 * j + q], xq);
+        wr[q] = row_sum<false>((m[j] >> (8 * q)) & 255u, v, xq, 1.0);
+      }
+      store_pair<NTY>(w + base + j * (2 * kT), wr[0], wr[1]);
+      store_pair<false>(pnew + base + j * (2 * kT), xc[2 * j], xc[2 * j + 1]);  // the update sweep reads p next
+      acc = acc + wr[0] * xc[2 * j];
+      acc = acc + wr[1] * xc[2 * j + 1];
+    }
+    acc = wave_butterfly(acc);
+    if (lane == 0) red[wv] = acc;
+    __syncthreads();
+    if (t == 0) partial[c] = (red[0] + red[1]) + (red[2] + red[3]);
+    planes_rotate(xm, xc, xp);
+  }
+}
+
 // The symmetric STENCIL fused step with two threads per DBR lane (round 5): 512 threads a tile, thread t < 256 takes
 // the lane's row pairs j = 0..3, thread t + 256 its pairs j = 4..7 -- half the registers of the one-thread form
 // (legs, x(z-1..z+1), uz), so a CU holds eight waves of it where it held four.  The rows' W values are exchanged
@@ -2917,6 +3028,34 @@ extern "C" int msk_box_spmv_mdot_rv(int32_t nx, int64_t P, int64_t n, int d2, co
 static bool box_mdot_marches(int32_t nx, int64_t P, int64_t n, int d2) {
   return !d2 && nx >= 2 && nx <= 2048 && P >= nx && P % kChunk == 0 && n > 0 && n % P == 0 && (nx & 1) == 0 &&
          !(msk_tuning_flags & MSK_TUNE_BOX_MDOT_FLAT) && !dv_flags_bad() && (n / P) <= INT32_MAX;
+}
+
+// 1 when msk_box_cg_march takes the box: the DV box stencils msk_box_spmv_mdot marches
+extern "C" int msk_box_cg_march_fits(int32_t nx, int64_t P, int64_t n, int d2) {
+  return box_mdot_marches(nx, P, n, d2) ? 1 : 0;
+}
+
+// KSPCG's AYPX + MatMult + self-dot stage 1 in one march (k_box_cg_march); dinv null: PCNONE.  The operands are
+// 16-byte aligned vectors of n doubles, pnew != pold.
+extern "C" int msk_box_cg_march(int32_t nx, int64_t P, int64_t n, int d2, const uint8_t* mask, const double* dval,
+                                const double* r, const double* dinv, const double* pold, const int* iter,
+                                const double* bdev, double* pnew, double* w, double* partial, int64_t nchunks,
+                                const int* stop, hipStream_t s) {
+  auto a16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+  if (!box_mdot_marches(nx, P, n, d2) || nchunks != n / kChunk || pnew == pold || !a16(r) || !a16(dinv) ||
+      !a16(pold) || !a16(pnew) || !a16(w))
+    return (int)hipErrorInvalidValue;
+  const int32_t nz = (int32_t)(n / P);
+  const TileGrid tg = tile_grid(nx, P, nz, 4, false, MSK_TUNE_BOX_MDOT_NOXCD);  // four planes per workgroup, as the
+  if (tg.grid > INT32_MAX) return (int)hipErrorInvalidValue;                      // fused MatMult + MDot
+  const bool nty = !(msk_tuning_flags & MSK_TUNE_ELL_TEMPORAL_Y);
+  pick<true, false>(dinv != nullptr, [&](auto jac) {
+    pick<true, false>(nty, [&](auto nt) {
+      k_box_cg_march<decltype(jac)::value, decltype(nt)::value><<<dim3((unsigned)tg.grid), dim3(kT), tg.lds, s>>>(
+          nx, P, nz, 4, tg.xcd1, mask, dval, r, dinv, pold, iter, bdev, pnew, w, partial, stop);
+    });
+  });
+  return (int)hipGetLastError();
 }
 
 // the boxes msk_box_spmv_mdot takes (marched or not)

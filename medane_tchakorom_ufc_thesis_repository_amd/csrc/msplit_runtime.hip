@@ -2022,6 +2022,42 @@ extern "C" int mspi_gm_wfree(const msp_mat* A) {
   return msk_box_wfree_fits(A->march_nx, (int64_t)A->march_nx * A->march_ny, A->nrows, A->march_d2);
 }
 
+// ---- KSPCG's routes for w = A p and p . w (msplit_internal.h MSPI_CG_ROUTE_*), asked once per solve
+// 1 when mspi_spmv_mdot(A, x, .., y != NULL, nv = 1, ..) launches its fused kernel (its own conditions, restated)
+extern "C" int mspi_spmv_mdot_takes(const msp_mat* A) {
+  const msp_ctx* c = A->ctx;
+  if (c->reduce != MSP_REDUCE_DBR || A->nrows <= 0) return 0;
+  const bool box_on = !(msk_get_tuning() & MSK_TUNE_GM_BOX_MDOT_OFF);
+  if (A->rv_on) return box_on;
+  if (A->dv_on && box_march(A) && A->march_nx <= 2048) return box_on;
+  return !(A->matfree || A->compressed || A->csr_released || A->nrows != A->ncols || A->lds_cap512 <= 0 ||
+           !(msk_get_tuning() & MSK_TUNE_GM_SPMV_MDOT));
+}
+
+// 1 when mspi_cg_march takes A: a DV box stencil whose planes hold whole DBR chunks, DBR reduction
+extern "C" int mspi_cg_march_fits(const msp_mat* A) {
+  const msp_ctx* c = A->ctx;
+  if (c->reduce != MSP_REDUCE_DBR || !A->dv_on || !box_march(A)) return 0;
+  return msk_box_cg_march_fits(A->march_nx, (int64_t)A->march_nx * A->march_ny, A->nrows, A->march_d2);
+}
+
+// pnew = z + st->b pold (pnew = z at st->i == 0), w = A pnew and st->pw = pnew . w in one march and a stage 2
+extern "C" int mspi_cg_march(msp_mat* A, const double* r, const double* dinv, const double* pold, double* pnew,
+                             double* w, mspi_cg_state* st) {
+  msp_ctx* c = A->ctx;
+  const int64_t n = A->nrows, nch = nchunks_of(n);
+  ARGCHK(mspi_cg_march_fits(A), MSP_ERR_SUP, "KSPCG's march on an operator that does not take it");
+  ARGCHK(nch <= c->partial_cap, MSP_ERR_ARG_WRONG, "KSPCG step without mspi_reserve_partial");
+  {
+    // the presence byte, r and pold read (and dinv), pnew and w written
+    KTimer kt(c, MSP_KERNEL_SPMVDOT, (double)n + 8.0 * (double)n * (dinv ? 5.0 : 4.0));
+    KCHK(msk_box_cg_march(A->march_nx, (int64_t)A->march_nx * A->march_ny, n, A->march_d2, A->march_mask, A->dv_val, r,
+                          dinv, pold, &st->i, &st->b, pnew, w, c->partial, nch, &st->stop, c->stream));
+  }
+  KCHK(msk_dot_stage2(c->partial, nch, 1, &st->pw, &st->stop, c->stream));
+  return MSP_SUCCESS;
+}
+
 // VV(it+1) = A (sc x) - sum_j h_j VV(j), x = VV(it) the basis' last vector, with the ||VV(it+1)||^2 partials
 // (k_box_maxpy_march), then the fold + Hessenberg update (k_norm_update) as mspi_maxpy_norm_update.
 extern "C" int mspi_maxpy_norm_update_march(msp_mat* A, const double* x, const double* sdev, double* wout, int nv,

@@ -205,6 +205,10 @@ def _gmres(ctx, opts, p):
     ksp = KSP(ctx)
     ksp.set_operators(A)
     ksp.set_from_options(opts)
+    if ksp.get_type() == "cg" and p["peclet"] is not None and any(v != 0.0 for v in p["peclet"]):
+        from .petsc import PETSC_ERR_SUP, MsplitError
+        raise MsplitError(PETSC_ERR_SUP, "-msplit_ksp_type cg with a non-zero -peclet: the convection-diffusion "
+                          "operator is not symmetric")
     ctx.synchronize()
     t0 = time.perf_counter()
     ksp.solve(b, x)

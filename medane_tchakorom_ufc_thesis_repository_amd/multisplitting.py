@@ -99,6 +99,9 @@ class GpuBlock:
         del ones
         self.opts = opts
         self.ksp = initializeKSP(ctx, self.A, False, self.prefix, opts)
+        if self.ksp.get_type() == "cg" and any(float(v) != 0.0 for v in self.peclet):
+            raise MsplitError(PETSC_ERR_SUP, f"-{self.prefix}msplit_ksp_type cg with a non-zero -peclet: the "
+                              "convection-diffusion operator is not symmetric")
         self.last_its = 0
 
     # -- exchange hooks (comm.py)

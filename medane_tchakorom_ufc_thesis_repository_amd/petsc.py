@@ -737,7 +737,8 @@ class LSQR:
 # ------------------------------------------------------------------------- KSP
 class KSP:
     """KSPGMRES with PCNONE or left PCJACOBI (PCNONE: the reference's canonical inner solver,
-    running_bulk_test_g5k:64-70; initializeKSP, utils.c:512-541)."""
+    running_bulk_test_g5k:64-70; initializeKSP, utils.c:512-541); set_type("cg"): KSPCG for the symmetric positive
+    definite blocks."""
 
     def __init__(self, ctx: Context):
         self.ctx = ctx
@@ -854,6 +855,36 @@ class KSP:
         call("msp_ksp_get_cgs_refinement", self.h, C.byref(v))
         return {n: w for w, n in self.CGS_REFINEMENTS.items()}[v.value]
 
+    # Krylov method (msp_ksp_set_type): "cg" is PETSc's KSPCG for the symmetric positive definite blocks, with
+    # PCNONE or left Jacobi and either norm; three work vectors whatever max_it is.  Double basis and operator, no
+    # CGS refinement, DBR reduction.
+    KSP_TYPES = {"gmres": 0, "cg": 1}
+    NORM_TYPES = {"preconditioned": 0, "unpreconditioned": 1}
+
+    def set_type(self, ksp_type: str):                              # KSPSetType
+        word = str(ksp_type).lower()
+        if word not in self.KSP_TYPES:
+            raise MsplitError(PETSC_ERR_ARG_OUTOFRANGE, f"KSP type {ksp_type!r}: expected one of "
+                                                        f"{sorted(self.KSP_TYPES)}")
+        call("msp_ksp_set_type", self.h, self.KSP_TYPES[word])
+
+    def get_type(self) -> str:                                      # KSPGetType
+        v = C.c_int()
+        call("msp_ksp_get_type", self.h, C.byref(v))
+        return {n: w for w, n in self.KSP_TYPES.items()}[v.value]
+
+    def set_norm_type(self, norm_type: str):                        # KSPSetNormType (read by "cg" only)
+        word = str(norm_type).lower()
+        if word not in self.NORM_TYPES:
+            raise MsplitError(PETSC_ERR_ARG_OUTOFRANGE, f"norm type {norm_type!r}: expected one of "
+                                                        f"{sorted(self.NORM_TYPES)}")
+        call("msp_ksp_set_norm_type", self.h, self.NORM_TYPES[word])
+
+    def get_norm_type(self) -> str:                                 # KSPGetNormType
+        v = C.c_int()
+        call("msp_ksp_get_norm_type", self.h, C.byref(v))
+        return {n: w for w, n in self.NORM_TYPES.items()}[v.value]
+
     def get_cgs_refinement_count(self) -> int:
         """Arnoldi steps of the last solve that ran the second Gram-Schmidt pass."""
         v = C.c_int32()
@@ -888,12 +919,30 @@ class KSP:
         p = self.prefix
         kt = opts.get_string("ksp_type", "gmres", p)
         if kt.lower() != "gmres":
-            raise MsplitError(PETSC_ERR_SUP, f"-{p}ksp_type {kt}: only gmres is implemented on the MI355X path")
+            raise MsplitError(PETSC_ERR_SUP, f"-{p}ksp_type {kt}: only gmres is read from -{p}ksp_type on the MI355X "
+                                             f"path; conjugate gradients are chosen with -{p}msplit_ksp_type cg")
+        # the library's own key for the Krylov method: -<prefix>ksp_type keeps meaning the reference's GMRES
+        mt = opts.get_string("msplit_ksp_type", self.get_type(), p).lower()
+        if mt not in self.KSP_TYPES:
+            raise MsplitError(PETSC_ERR_ARG_OUTOFRANGE, f"-{p}msplit_ksp_type {mt}: expected one of "
+                                                        f"{sorted(self.KSP_TYPES)}")
+        cg = mt == "cg"
         pt = opts.get_string("pc_type", self.get_pc_type(), p)
         if pt.lower() not in self.PC_TYPES:
             raise MsplitError(PETSC_ERR_SUP, f"-{p}pc_type {pt}: only none and jacobi are implemented on the "
                                              "MI355X path")
-        if pt.lower() == "jacobi":
+        if cg:
+            side = opts.get_string("ksp_pc_side", "left", p).lower()
+            if side != "left":
+                raise MsplitError(PETSC_ERR_SUP, f"-{p}ksp_pc_side {side} with -{p}msplit_ksp_type cg: only left "
+                                                 "preconditioning is implemented")
+            if pt.lower() == "jacobi":
+                jt = opts.get_string("pc_jacobi_type", "diagonal", p).lower()
+                if jt != "diagonal":
+                    raise MsplitError(PETSC_ERR_SUP, f"-{p}pc_jacobi_type {jt}: only diagonal is implemented")
+                if opts.get_bool("pc_jacobi_abs", False, p):
+                    raise MsplitError(PETSC_ERR_SUP, f"-{p}pc_jacobi_abs is not implemented")
+        elif pt.lower() == "jacobi":
             self._check_jacobi_options(opts, p)
         if opts.has("ksp_gmres_modifiedgramschmidt", p):
             raise MsplitError(PETSC_ERR_SUP, "modified Gram-Schmidt is not implemented (CGS only)")
@@ -908,7 +957,11 @@ class KSP:
                                                  "refine_ifneeded")
         nt = opts.get_string("ksp_norm_type", "preconditioned", p).lower()
         if nt not in ("preconditioned", "unpreconditioned"):
-            raise MsplitError(PETSC_ERR_SUP, f"-{p}ksp_norm_type {nt} not supported by GMRES")
+            raise MsplitError(PETSC_ERR_SUP, f"-{p}ksp_norm_type {nt} not supported by " + ("CG" if cg else "GMRES"))
+        if opts.has("msplit_ksp_type", p):
+            self.set_type(mt)
+        if cg and opts.has("ksp_norm_type", p):
+            self.set_norm_type(nt)
         o = self.get_opts()
         o.restart = opts.get_int("ksp_gmres_restart", o.restart, p)
         o.max_it = opts.get_int("ksp_max_it", o.max_it, p)

@@ -5,6 +5,7 @@
 //   read K   : s += V_j[i] for j < K (a store of one double per lane so nothing is dead code)
 //   copy     : y = x
 //   mix K    : y = x + sum_{j<K} V_j (K + 1 reads : 1 write, the CGS VecMAXPY's mix)
+//   rw42     : x += p ; r += w in place (4 reads : 2 writes, the KSPCG update sweep's mix)
 //   fill     : y = c
 // Prints one JSON object: TB/s per kernel (bytes the kernel requests / time per launch, HIP events).
 //   hipcc -O3 --offload-arch=gfx950 -std=c++17 tools/stream_ceiling.hip -o tools/stream_ceiling
@@ -65,6 +66,23 @@ __global__ __launch_bounds__(kT) void k_mix(const double* __restrict__ x, const 
   }
 #pragma unroll
   for (int j = 0; j < kIt; ++j) st(y + base + j * 2 * kT, u[j]);
+}
+
+// x += p ; r += w, both in place: 4 reads and 2 writes per element, KSPCG's update sweep without its sums
+__global__ __launch_bounds__(kT) void k_rw42(double* __restrict__ x, const double* __restrict__ p,
+                                             double* __restrict__ r, const double* __restrict__ w) {
+  const int64_t base = (int64_t)blockIdx.x * kChunk + 2 * threadIdx.x;
+  dx2 a[kIt], b[kIt];
+#pragma unroll
+  for (int j = 0; j < kIt; ++j) {
+    a[j] = ld(x + base + j * 2 * kT) + ld(p + base + j * 2 * kT);
+    b[j] = ld(r + base + j * 2 * kT) + ld(w + base + j * 2 * kT);
+  }
+#pragma unroll
+  for (int j = 0; j < kIt; ++j) {
+    st(x + base + j * 2 * kT, a[j]);
+    st(r + base + j * 2 * kT, b[j]);
+  }
 }
 
 __global__ __launch_bounds__(kT) void k_copy(const double* __restrict__ x, double* __restrict__ y) {
@@ -137,7 +155,9 @@ int main(int argc, char** argv) {
     ms = time_ms([&] { k_mix<8><<<g, kT>>>(x, V, stride, K, y); }, reps);
     printf(", \"mix%d_u8_TBps\": %.3f", K, B * (K + 2) / (ms * 1e-3) / 1e12);
   }
-  double ms = time_ms([&] { k_copy<<<g, kT>>>(x, y); }, reps);
+  double ms = time_ms([&] { k_rw42<<<g, kT>>>(x, V, y, V + stride); }, reps);  // V's vectors are zeros
+  printf(", \"rw42_TBps\": %.3f", 6 * B / (ms * 1e-3) / 1e12);
+  ms = time_ms([&] { k_copy<<<g, kT>>>(x, y); }, reps);
   printf(", \"copy_TBps\": %.3f", 2 * B / (ms * 1e-3) / 1e12);
   ms = time_ms([&] { k_fill<<<g, kT>>>(y, 1.0); }, reps);
   printf(", \"fill_TBps\": %.3f}\n", B / (ms * 1e-3) / 1e12);
