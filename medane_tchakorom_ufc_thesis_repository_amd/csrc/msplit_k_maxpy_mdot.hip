@@ -151,7 +151,7 @@ extern "C" int msk_maxpy_mdot(const double* win, double* wout, const Vecs* V, in
                               double* partial, int64_t nchunks, const int* stop, hipStream_t s) {
   if (n <= 0 || nchunks <= 0) return 0;
   if (nv < 1 || nv + 1 > MSK_MAX_GROUP) return (int)hipErrorInvalidValue;  // partial has MSK_MAX_GROUP rows
-  const int rev = n > ((int64_t)1 << 25);  // msk_maxpy_chunk's rule
+  const int rev = maxpy_rev(n);  // msk_maxpy_chunk's order
   // the store policy follows MSK_TUNE_MAXPY_TEMPORAL_ST; the basis loads are non-temporal
   pick<1, 5>((msk_tuning_flags & MSK_TUNE_MAXPY_TEMPORAL_ST) ? 1 : 5, [&](auto var) {
     pick_range<1, MSK_MAX_GROUP - 1>(nv, [&](auto k) {

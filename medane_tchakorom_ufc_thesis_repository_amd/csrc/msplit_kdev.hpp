@@ -338,6 +338,8 @@ __device__ __forceinline__ double group_sum(const double (&a)[G], const double (
 // ===================================================================== launchers
 // Tuning flags (A/B experiments; MSPLIT_TUNING at context creation), defined in msplit_kernels.hip.
 extern __attribute__((visibility("hidden"))) int msk_tuning_flags;
+// MAXPY's chunk order, -1 (by size), 0 or 1 (maxpy_rev below), defined in msplit_kernels.hip.
+extern __attribute__((visibility("hidden"))) int msk_maxpy_rev_forced;
 
 // The row-block schedule msk_spmv gives an operator of this shape, {bp, gb, np} of XcdMap (msplit_kernels.hip)
 __attribute__((visibility("hidden"))) void msk_xcd_map3(int32_t nrows, int64_t plane, int32_t out[3]);
@@ -385,11 +387,11 @@ inline int env_int(const char* name, int dflt) {
 // basis-vector load policy: non-temporal unless MSK_TUNE_VEC_TEMPORAL (A/B)
 inline int vec_var() { return (msk_tuning_flags & MSK_TUNE_VEC_TEMPORAL) ? 0 : 1; }
 
-// MAXPY's chunk order (msk_maxpy_chunk, msk_box_maxpy_march): top chunks first where a vector outgrows the 256 MiB
-// MALL (n > 2^25); MSPLIT_MAXPY_REV=0/1 forces either order.
+// MAXPY's chunk order (msk_maxpy_chunk, msk_maxpy_mdot, msk_box_maxpy_march): top chunks first where a vector
+// outgrows the 256 MiB MALL (n > 2^25); msk_maxpy_rev_forced (msplit_kernels.hip: MSPLIT_MAXPY_REV, msk_set_maxpy_rev)
+// forces either order, -1 leaves it to n.
 inline bool maxpy_rev(int64_t n) {
-  static const int forced = getenv("MSPLIT_MAXPY_REV") ? (env_int("MSPLIT_MAXPY_REV", 0) ? 1 : 0) : -1;
-  return forced < 0 ? n > ((int64_t)1 << 25) : forced != 0;
+  return msk_maxpy_rev_forced < 0 ? n > ((int64_t)1 << 25) : msk_maxpy_rev_forced != 0;
 }
 
 // MDot stage 1 is launched from three units (msplit_k_dot.hip: the default variant; msplit_k_dot_a.hip and

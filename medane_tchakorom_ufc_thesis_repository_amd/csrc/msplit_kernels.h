@@ -179,6 +179,11 @@ int msk_get_gm_wfree(void);
 // MSPLIT_MAXPY_PREFETCH; the setter re-keys captured cycles.  Every setting gives the same bits.
 void msk_set_maxpy_prefetch(int mode);
 int msk_get_maxpy_prefetch(void);
+// The workgroup-to-chunk order of msk_maxpy_chunk, msk_maxpy_mdot and msk_box_maxpy_march: -1 top chunks first
+// where n > 2^25 (the default), 0 bottom first, 1 top first.  Default from MSPLIT_MAXPY_REV; the setter re-keys
+// captured cycles.  Either order gives the same bits.
+void msk_set_maxpy_rev(int rev);
+int msk_get_maxpy_rev(void);
 int msk_box_wfree_fits(int32_t nx, int64_t P, int64_t n, int d2);
 int msk_box_maxpy_march(int32_t nx, int64_t P, int64_t n, int d2, const uint8_t* mask, const double* dval, const double* x,
                         const double* sdev, double* wout, const Vecs* V, int nv, const double* adev, double* partial,

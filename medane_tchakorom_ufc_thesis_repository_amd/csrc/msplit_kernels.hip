@@ -2541,6 +2541,17 @@ extern "C" void msk_set_maxpy_prefetch(int mode) {
   ++msk_shape_epoch;
 }
 extern "C" int msk_get_maxpy_prefetch(void) { return msk_maxpy_prefetch; }
+// MAXPY's chunk order (maxpy_rev in msplit_kdev.hpp): -1 top chunks first where n > 2^25, 0 never, 1 always.
+// MSPLIT_MAXPY_REV, read when the library is loaded, sets the default (unset: -1; set: 1 unless it reads as 0);
+// after that only the setter changes it.  msk_set_maxpy_rev switches it (tests)
+// and re-keys captured cycles, which bake the order in.  Either order gives the same bits.
+__attribute__((visibility("hidden"))) int msk_maxpy_rev_forced =
+    getenv("MSPLIT_MAXPY_REV") ? (env_int("MSPLIT_MAXPY_REV", 0) ? 1 : 0) : -1;
+extern "C" void msk_set_maxpy_rev(int rev) {
+  msk_maxpy_rev_forced = rev < 0 ? -1 : rev ? 1 : 0;
+  ++msk_shape_epoch;
+}
+extern "C" int msk_get_maxpy_rev(void) { return msk_maxpy_rev_forced; }
 
 static inline XcdMap xcd_map(int32_t nrows, int64_t plane) {
   XcdMap m = {0, 0, 0};

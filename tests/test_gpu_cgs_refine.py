@@ -16,10 +16,11 @@ import os
 import numpy as np
 import pytest
 
+import dbr_fold as df
 import oper_twin as ot
 import refine_twin as rt
 from gmres_step import GmresDev, StepWork, bind, last_error
-from guarded import GUARD_BITS, SLACK, UNWRITTEN_BITS, assert_same_bits, same_bits
+from guarded import GUARD_BITS, SLACK, UNWRITTEN_BITS, Guarded, assert_same_bits, same_bits
 from medane_tchakorom_ufc_thesis_repository_amd import MsplitError, _lib
 from medane_tchakorom_ufc_thesis_repository_amd.petsc import KSP, Mat, Options, Vec
 from medane_tchakorom_ufc_thesis_repository_amd.utils import heterogeneous_poisson3d
@@ -236,9 +237,12 @@ class Block:
         _ok(self.L.mspi_gm_refine_decide(self.ctx.h, self.w.g, self.rf.device_ptr(), partial, nchunks))
         self.ctx.synchronize()
 
-    def update(self, ss2=None):
-        pv = Vec.from_array(self.ctx, np.array([ss2 if ss2 is not None else np.nan, np.nan]))
-        _ok(self.L.mspi_gm_refine_update(self.ctx.h, self.w.g, self.rf.device_ptr(), pv.device_ptr(), 1, M))
+    def update(self, ss2=None, partial=None, nchunks=1):
+        """ss2 handed over as one partial, or partial: a device array of nchunks partials of it."""
+        if partial is None:
+            pv = Vec.from_array(self.ctx, np.array([ss2 if ss2 is not None else np.nan, np.nan]))
+            partial = pv.device_ptr()
+        _ok(self.L.mspi_gm_refine_update(self.ctx.h, self.w.g, self.rf.device_ptr(), partial, nchunks, M))
         self.ctx.synchronize()
 
 
@@ -309,6 +313,45 @@ def test_decide_folds_the_fused_pass_partials(ctx, oracle):
     for v in op.h:
         hsq = hsq + v * v
     assert hdr.refine == int(np.sqrt(s[96]) < np.sqrt(hsq))
+
+
+@pytest.mark.parametrize("mode", [ALWAYS, IFNEEDED], ids=["always", "ifneeded"])
+@pytest.mark.parametrize("nch", df.NCH_THIN)
+def test_decide_and_update_fold_many_chunks(ctx, nch, mode):
+    """fold_partials beyond one trip per lane (tests/dbr_fold.py: the second trip, the 8-deep and the 16-deep loop,
+    one after the other), on synthetic partials in guarded windows: the decide kernel's c_j and ss1 and the update
+    kernel's ss2 are fold() of their rows bit for bit, the decision is the one those sums give, and the recurrence
+    is k_norm_update's on the column and the sum they give."""
+    for name in df.NAMES:
+        seed = 31 * nch + 7 * mode
+        rows = [df.data_sets(nch, seed + r)["mixed" if r != 1 else name] for r in range(IT + 1)]      # c_0 .. c_it
+        rows.append(df.data_sets(nch, seed + 5, signed=False)[name])                                   # ||u||^2
+        ss2row = df.data_sets(nch, seed + 6, signed=False)[name]
+        cw = np.array([df.fold(r) for r in rows[:IT + 1]])
+        ss1, ss2 = df.fold(rows[IT + 1]), df.fold(ss2row)
+        p1 = Guarded.input(ctx, np.concatenate(rows), Operands.LEAD)
+        p2 = Guarded.input(ctx, ss2row, Operands.LEAD)
+        b = Block(ctx, mode, H, [], -1.0)
+        b.decide(p1.vec.device_ptr(), nch)
+        hdr, c, guard = b.block()
+        what = f"{name}, {nch} chunks"
+        assert_same_bits(c[:IT + 1], cw, f"c folded by the decide kernel, {what}")
+        assert_same_bits(hdr.ss1, ss1, f"ss1 folded by the decide kernel, {what}")
+        with np.errstate(invalid="ignore"):
+            wnrm = np.sqrt(ss1)
+        refine = 1 if mode == ALWAYS else int(bool(np.isfinite(wnrm) and wnrm < HNRM))
+        assert (hdr.refine, hdr.skip, hdr.count) == (refine, 1 - refine, 4 + refine), what
+        assert (guard.view(np.uint64) == GUARD_BITS).all() and not c[IT + 1:].any()
+        if not refine and not np.isfinite(wnrm):
+            continue                                   # KSPCheckNorm's branch folds nothing (test_nan_ss1_...)
+        b.update(partial=p2.vec.device_ptr(), nchunks=nch)
+        hdr, _, guard = b.block()
+        assert hdr.skip == 1 and (guard.view(np.uint64) == GUARD_BITS).all()
+        assert_same_bits(hdr.ss2, ss2 if refine else -7.0, f"ss2 folded by the update kernel, {what}")
+        col = (np.float64(0.0) - (-H)) - (-cw) if refine else H
+        _same_recurrence(b.w, _reference_update(ctx, col, ss2 if refine else ss1), what)
+        p1.check()
+        p2.check()
 
 
 def test_nan_ss1_ends_the_cycle_like_a_nan_dot(ctx):

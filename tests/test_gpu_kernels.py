@@ -140,7 +140,7 @@ def test_mdot_bitwise_dbr(ctx, oracle, nv, n, flags):
     assert np.array_equal(got, oracle.mdot(w, V, oracle.REDUCE_DBR))
 
 
-@pytest.mark.parametrize("flags", [0, MAXPY_UNROLL1, MAXPY_HALVES, MAXPY_HALVES | MAXPY_UNROLL1,
+@pytest.mark.parametrize("flags", [0, MAXPY_UNROLL1, MAXPY_HALVES, MAXPY_HALVES | MAXPY_UNROLL1, MAXPY_TEMPORAL_ST,
                                    VEC_TEMPORAL | MAXPY_TEMPORAL_ST, VEC_TEMPORAL | MAXPY_TEMPORAL_ST | MAXPY_UNROLL1])
 @pytest.mark.parametrize("nv", [1, 2, 3, 4, 5, 6, 7, 8, 13, 30, 31, 32, 33, 37, 64, 65])
 @pytest.mark.parametrize("n", [1, 7, 4096, 10001])

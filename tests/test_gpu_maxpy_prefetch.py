@@ -44,15 +44,20 @@ def _L():
 
 
 @contextmanager
-def prefetch(mode):
-    L = _L()
-    old = L.msk_get_maxpy_prefetch()
-    L.msk_set_maxpy_prefetch(mode)
+def switched(get, set_, value):
+    """A library switch with a getter and a setter, at value inside the block and back at what it was after it."""
+    old = get()
+    set_(value)
     try:
-        assert L.msk_get_maxpy_prefetch() == mode
+        assert get() == value
         yield
     finally:
-        L.msk_set_maxpy_prefetch(old)
+        set_(old)
+
+
+def prefetch(mode):
+    L = _L()
+    return switched(L.msk_get_maxpy_prefetch, L.msk_set_maxpy_prefetch, mode)
 
 
 def _make(ctx, shape, peclet):
@@ -247,11 +252,12 @@ def _in_process(env):
 
 def test_zt_and_rev_settings(ctx, oracle):
     """MSPLIT_MAXPY_ZT=2 (two planes per workgroup: the switch must leave the marched form in place) and
-    MSPLIT_MAXPY_REV=1 (top planes first, with the one-plane form) are read once per process.  Each process solves
-    with the switch at 0, 2 and 3; every result is this process's oracle-checked reference."""
+    MSPLIT_MAXPY_REV=1 (top planes first, with the one-plane form) are read once per process; both together start
+    on the ragged top group (nz = 5: plane 4 alone).  Each process solves with the switch at 0, 2 and 3; every
+    result is this process's oracle-checked reference."""
     A, b, ref = _reference(ctx, oracle, (64, 64, 5), None, 30, 40, seed=7)
     want = {"hist": [float(h).hex() for h in ref[1]], "x": hashlib.sha256(ref[2].tobytes()).hexdigest()}
-    for env in ({"MSPLIT_MAXPY_ZT": "2"}, {"MSPLIT_MAXPY_REV": "1"}):
+    for env in ({"MSPLIT_MAXPY_ZT": "2"}, {"MSPLIT_MAXPY_REV": "1"}, {"MSPLIT_MAXPY_ZT": "2", "MSPLIT_MAXPY_REV": "1"}):
         got = _in_process(env)
         for mode in ("0", "2", "3"):
             assert got[mode] == want, (env, mode)
